@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — the TiPS gradient-bucket reduction path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...     (N > 1, one rank per GPU)
+
+A plain run does what the headline needs and no more: it sets up, runs W warm-up steps, times K
+steps, writes the last timed step's output under DIR if asked (--dump-outputs: `c` at N == 1, `out`
+for the allreduce workloads, as .npy; a fixed seeded sample where the output is above the 64 MB
+cap) and prints the line. Everything else described below - the parity checks, the CPU baselines,
+the sub-records, the per-kernel rooflines, the comparison schedules, probes and child jobs - runs
+only with --full.
 
 One JSON line (rank 0). Its headline `value` is BASELINE.json's metric:
 
@@ -78,7 +85,53 @@ def parse():
     ap.add_argument("--workload", default="auto", choices=["auto", "sum", "bucket", "fused1000", "resnet50", "negotiated1000"],
                     help="auto: config 2 (sum) at N=1, config 3 (bucket allreduce) at N>1, with the other configs "
                          "as sub-records; any other: that workload alone as the headline")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its parity check, the CPU baselines, the other configs as sub-records, "
+                         "the per-kernel rooflines, the comparison schedules, probes and child jobs (the --no-* "
+                         "options then leave single parts out). Without it a run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of an output above the size cap)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # the headline alone
+        args.no_cpu_baseline = args.no_compare = args.no_sub = args.no_env_variants = args.no_extras = True
+    return args
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+
+DUMP_CAP_BYTES = 64 * 1000 * 1000   # all files of one --dump-outputs together stay under this
+DUMP_SAMPLE_SEED = 20261019
+
+
+def dump_outputs(torch, directory, arrays):
+    """--dump-outputs: `arrays` (name -> 1-D float device tensor, what the last timed step handed its
+    caller) as directory/<name>.npy, float32 (float64 for an f64 tensor). Every array gets an equal
+    share of DUMP_CAP_BYTES; one above its share is written as a sample: its elements at
+    sorted indices drawn once from numpy's default_rng(DUMP_SAMPLE_SEED), the same for every run of
+    the same arguments. Returns what was written, for the result line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_CAP_BYTES - 4096 * len(arrays)) // max(1, len(arrays))  # (4 KiB each for the .npy headers)
+    wrote = {}
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.dtype != torch.float64:
+            t = t.float()
+        n, es = t.numel(), t.element_size()
+        entry = {"file": name + ".npy", "dtype": "f64" if es == 8 else "f32", "elements": n}
+        if n * es > share:
+            k = share // es
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, n, size=k, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            entry.update(sampled=k, sample="elements at sorted(default_rng(%d).integers(0, %d, size=%d))"
+                                           % (DUMP_SAMPLE_SEED, n, k))
+        np.save(os.path.join(directory, name + ".npy"), t.cpu().numpy())
+        wrote[name] = entry
+    return wrote
 
 
 # ----------------------------------------------------------------------------- CPU baselines (rank 0)
@@ -854,7 +907,7 @@ def child_bucket_jobs(args, dist, rank, world, specs, timeout_s=240):
             s_.close()
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                    "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__),
-                   "--gpus", str(world), "--steps", "10", "--warmup", "2", "--algo", algo, "--no-compare",
+                   "--gpus", str(world), "--steps", "10", "--warmup", "2", "--algo", algo, "--full", "--no-compare",
                    "--no-sub", "--no-cpu-baseline", "--no-env-variants"] + \
                 (["--bucket-mib", str(args.bucket_mib)] if args.bucket_mib else [])
             cenv = {k: v for k, v in os.environ.items()
@@ -1047,7 +1100,12 @@ def sum_record(args, cpu):
         step(i)
     torch.cuda.synchronize()
     ms, wall = timed(steps, same_buffers=False)
-    ok = all(bool(torch.equal(z_, x_ + y_)) for x_, y_, z_ in sets)  # one IEEE add per element: bit-exact
+    dumped = None
+    if args.dump_outputs:  # the last timed step's c (step steps - 1 summed triple (steps - 1) % ROTATING_SETS)
+        dumped = dump_outputs(torch, args.dump_outputs, {"c": sets[(steps - 1) % len(sets)][2]})
+    ok = True
+    if args.full:
+        ok = all(bool(torch.equal(z_, x_ + y_)) for x_, y_, z_ in sets)  # one IEEE add per element: bit-exact
 
     same = None
     if not args.no_extras:
@@ -1134,9 +1192,11 @@ def sum_record(args, cpu):
         "host_allreduce_gib_s": host_rates,
         "host_allreduce_note": "tips_allreduce(host in, host out) on one rank, 256 MiB: staged H2D + device + D2H, "
                                "bucket bytes / median wall time of 5 calls (all 5 listed)" + ("" if host_ok else " (RESULT MISMATCH)"),
-        "check": "bit-exact vs torch a+b" if ok else "FAIL",
+        "check": ("bit-exact vs torch a+b" if ok else "FAIL") if args.full else "not run (--full checks the result)",
         "wall_s_timed_region": round(wall, 4),
     }
+    if dumped:
+        line["dumped_outputs"] = dumped
     if tr:
         line["roofline"]["traffic_source"] = tr["source"]
     return line, ok
@@ -1213,6 +1273,7 @@ class Workload(object):
         self.h_arr = (ctypes.c_int64 * len(sizes))()
         self.fallbacks = []
         self.tuned = None
+        self.dump_dir = None  # (the headline's: --dump-outputs)
 
     def fill(self, t, r):
         self.g.manual_seed(self.seed0 + r)
@@ -1327,10 +1388,27 @@ class Workload(object):
         self.host_split = dict(self.host_t)
         self.ms = t / self.steps * 1e3
         progress(job.rank, "%s: %.3f ms per step" % (self.workload, self.ms))
-        ok, check = self.parity(self.algo)
-        self.ok = all_ranks_ok(job.dist, ok)
-        progress(job.rank, "%s parity: %s" % (self.workload, check))
-        return self.record(check, (w1[0] - w0[0], w1[1] - w0[1]))
+        dumped = None
+        if self.dump_dir and job.rank == 0:  # (every rank holds the same reduced values)
+            dumped = dump_outputs(job.torch, self.dump_dir, {"out": self.last_output()})
+        if job.args.full:
+            ok, check = self.parity(self.algo)
+            self.ok = all_ranks_ok(job.dist, ok)
+            progress(job.rank, "%s parity: %s" % (self.workload, check))
+        else:
+            self.ok, check = True, "not run (--full checks the result)"
+        rec = self.record(check, (w1[0] - w0[0], w1[1] - w0[1]))
+        if dumped:
+            rec["dumped_outputs"] = dumped
+        return rec
+
+    def last_output(self):
+        """What the last timed step handed its caller: the bucket's output buffer, or the gradients
+        of the set it reduced in place, one after the other."""
+        if self.workload == "bucket":
+            return self.y
+        x = self.rot_sets[(self.ctr - 1) % self.rot][0]
+        return self.job.torch.cat([x[o:o + k] for o, k in zip(self.offs, self.sizes)])
 
     def record(self, check, waits):
         job, world, _lib = self.job, self.job.world, self.job._lib
@@ -1374,9 +1452,10 @@ class Workload(object):
                 if tr:
                     rec["roofline"]["traffic"] = round(tr["bytes"])
                     rec["roofline"]["traffic_source"] = tr["source"]
-            if self.measure_pack:  # the dominant kernel (fusion pack / unpack) timed per launch; the step beside it
+            if self.measure_pack:
                 rec["fusion_one_rank"] = ("TIPS_FUSION_MEASURE_PACK=1: buckets packed and unpacked as at N > 1 (the "
                                           "default one-rank path does no bucket work)")
+            if self.measure_pack and job.args.full:  # the dominant kernel (fusion pack / unpack) timed per launch; the step beside it
                 rec["step_roofline"] = rec["roofline"]
                 rec["step_roofline"]["note"] = "whole eager step (launches, stream joins, table lookup)" + \
                     rec["step_roofline"]["note"][len("one rank"):]
@@ -1393,7 +1472,7 @@ class Workload(object):
             rec["host_us_per_tensor"] = {k: round(v / self.steps / len(self.sizes) * 1e6, 2) for k, v in self.host_split.items()}
             rec["api"] = "tips_enqueue_allreduce_n + tips_wait_n (1000 named requests, one call each way)"
             rec["response_cache"] = "on" if os.environ.get("TIPS_RESPONSE_CACHE", "1") != "0" else "off"
-            if world > 1 and self.job.args.workload == "auto":  # (a sub-record at N > 1: the list API only)
+            if (world > 1 and self.job.args.workload == "auto") or not job.args.full:  # (a sub-record at N > 1: the list API only)
                 return rec
             self.per_call = True  # the same requests through one ctypes call per tensor, for comparison
             for _ in range(2):
@@ -1866,7 +1945,7 @@ def bench_job(args):
     workload = args.workload if args.workload != "auto" else ("sum" if world == 1 else "bucket")
     headline_sum = workload == "sum"
     # CPU baselines first, on rank 0, before this process touches the GPU (they start child processes)
-    topo = gpu_topology() if rank == 0 and world > 1 else None
+    topo = gpu_topology() if rank == 0 and world > 1 and args.full else None
     cpu = None
     if rank == 0 and not args.no_cpu_baseline:
         if headline_sum:
@@ -1895,6 +1974,7 @@ def bench_job(args):
         steps = args.steps if args.steps is not None else 20
         warmup = args.warmup if args.warmup is not None else 5
         w = Workload(job, workload, steps, warmup)
+        w.dump_dir = args.dump_outputs
         rec = w.run()
         all_ok = w.ok
         line = {"metric": METRIC, "value": rec.pop("value"), "unit": rec.pop("unit"), "n_gpus": world, "steps": steps,
@@ -1909,10 +1989,10 @@ def bench_job(args):
                            if world > 1 else "single GPU: no link carries anything (the allreduce of one rank is the identity)"},
                 "cpu_baseline": cpu}
         line.update(rec)
-        kr = w.reduce_kernel_roofline()
+        kr = w.reduce_kernel_roofline() if args.full else None
         if kr:
             line["reduce_kernel_roofline"] = kr
-        if workload in SUB_WORKLOADS:
+        if workload in SUB_WORKLOADS and args.full:
             line["gradient_api"] = gradient_api_legs(torch, dist, tips_amd, world, w.sizes, w.offs, w.rot_sets, steps, w.ms)
             if workload == "resnet50":
                 host_legs(job, w, line)
@@ -1923,7 +2003,8 @@ def bench_job(args):
     _RESULT["line"] = line if rank == 0 else None
     _RESULT["done"] = True
     # (mandatory on every N > 1 line; a peer-schedule child job skips it: its parent line has it)
-    if w is not None and workload == "bucket" and world > 1 and os.environ.get("TIPS_BENCH_CHILD_NO_RING") != "1":
+    if w is not None and workload == "bucket" and world > 1 and args.full and \
+            os.environ.get("TIPS_BENCH_CHILD_NO_RING") != "1":
         north_star_ring(job, w, line)  # mandatory, before every sub-record and budgeted leg
         _RESULT["line"] = line if rank == 0 else None
     if args.workload == "auto" and not args.no_sub:

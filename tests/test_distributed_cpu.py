@@ -364,3 +364,51 @@ def test_peer_child_that_hangs_costs_only_its_entry():
         assert "timed out" in line0["peer_children"][name]["error"], line0
         assert line0["compare_algbw_gib_s"][name] is None and line0["compare_check"][name].startswith("error: timed out")
     assert res[1][1]["peer_children"] == {}  # (the other ranks only wait)
+
+
+def test_bench_plain_run_is_the_headline_alone(monkeypatch):
+    """bench.parse: without --full every optional part is off (as if each --no-* option were given);
+    with it they run unless a --no-* option names them. --steps below 1 is refused."""
+    sys.path.insert(0, REPO)
+    import bench
+    parts = ("no_cpu_baseline", "no_compare", "no_sub", "no_env_variants", "no_extras")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert all(getattr(a, k) for k in parts)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-sub", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    assert {k for k in parts if getattr(a, k)} == {"no_sub"}
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_cap_and_sample(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 .npy files (float64 for an f64 array); an array within its share
+    of the cap is written whole, a larger one as the elements at seeded, sorted indices - the same
+    ones on every call; all files together stay under the cap."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.DUMP_CAP_BYTES <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 1 << 20)  # (the same code path at a test's size)
+    big = torch.arange(1 << 20, dtype=torch.float32) * 0.5
+    small = torch.linspace(0, 1, 1000, dtype=torch.float64)
+    half = torch.arange(300, dtype=torch.float16)
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    w = bench.dump_outputs(torch, d1, {"big": big, "small": small, "half": half})
+    bench.dump_outputs(torch, d2, {"big": big, "small": small, "half": half})
+    got = {k: np.load(os.path.join(d1, k + ".npy")) for k in ("big", "small", "half")}
+    assert sorted(os.listdir(d1)) == ["big.npy", "half.npy", "small.npy"]
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in os.listdir(d1)) <= 1 << 20
+    assert got["small"].dtype == np.float64 and np.array_equal(got["small"], small.numpy())
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], np.arange(300, dtype=np.float32))
+    assert "sampled" not in w["small"] and w["big"]["elements"] == 1 << 20
+    k = w["big"]["sampled"]
+    assert got["big"].dtype == np.float32 and got["big"].shape == (k,) and (1 << 16) < k < (1 << 20) // 4
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, 1 << 20, size=k, dtype=np.int64))
+    assert np.array_equal(got["big"], big.numpy()[idx])
+    assert np.array_equal(got["big"], np.load(os.path.join(d2, "big.npy")))

@@ -10,7 +10,7 @@ for round in 1 2 3; do
   for w in fused1000 resnet50; do
     for v in 0 1; do
       printf '== %s caller_stream %s ' "$w" "$v" >> "$OUT/fusion_stream_ab.txt"
-      TIPS_FUSION_CALLER_STREAM=$v timeout -k 5 120 python bench.py --workload $w --no-sub --no-cpu-baseline 2>/dev/null \
+      TIPS_FUSION_CALLER_STREAM=$v timeout -k 5 120 python bench.py --workload $w --full --no-sub --no-cpu-baseline 2>/dev/null \
         | grep '^{' >> "$OUT/fusion_stream_ab.txt"
     done
   done

@@ -32,15 +32,15 @@ for s in ${STEPS:-pytest bench1}; do
   case $s in
     pytest) run pytest "${PYTEST_TIMEOUT:-1100}" python -u -m pytest ${PYTEST_ARGS:-tests -m gpu} -x -q --timeout 300 \
               --timeout-method thread > "$OUT/pytest.log" 2>&1 || exit $? ;;
-    bench1) run bench1 "${BENCH_TIMEOUT:-500}" python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench_n1.jsonl" \
+    bench1) run bench1 "${BENCH_TIMEOUT:-500}" python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_n1.jsonl" \
               2> "$OUT/bench_n1.err" || exit $? ;;
     bench1prof) run bench1prof 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py \
                   --no-sub --no-cpu-baseline --no-extras --steps 200 --warmup 20 > "$OUT/bench_prof.log" 2>&1 || exit $? ;;
-    rehearse2) TIPS_BENCH_FAKE_HOSTS=1 run rehearse2 "${N2_TIMEOUT:-600}" python -u bench.py --gpus 2 ${REHEARSE_ARGS:-} \
+    rehearse2) TIPS_BENCH_FAKE_HOSTS=1 run rehearse2 "${N2_TIMEOUT:-600}" python -u bench.py --gpus 2 --full ${REHEARSE_ARGS:-} \
                  > "$OUT/rehearsal_n2.log" 2>&1 || exit $? ;;
-    rehearse4) TIPS_BENCH_FAKE_HOSTS=1 run rehearse4 "${N4_TIMEOUT:-700}" python -u bench.py --gpus 4 ${REHEARSE_ARGS:-} \
+    rehearse4) TIPS_BENCH_FAKE_HOSTS=1 run rehearse4 "${N4_TIMEOUT:-700}" python -u bench.py --gpus 4 --full ${REHEARSE_ARGS:-} \
                  > "$OUT/rehearsal_n4.log" 2>&1 || exit $? ;;
-    rehearse8) TIPS_BENCH_FAKE_HOSTS=1 run rehearse8 "${N8_TIMEOUT:-700}" python -u bench.py --gpus 8 ${REHEARSE_ARGS:-} \
+    rehearse8) TIPS_BENCH_FAKE_HOSTS=1 run rehearse8 "${N8_TIMEOUT:-700}" python -u bench.py --gpus 8 --full ${REHEARSE_ARGS:-} \
                  > "$OUT/rehearsal_n8.log" 2>&1 || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit $? ;;
     custom) run custom "${CUSTOM_TIMEOUT:-600}" bash -c "$CUSTOM" > "$OUT/custom.log" 2>&1 || exit $? ;;

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 ( while sleep 45; do date +%T >> "$OUT/heartbeat.txt"; done ) &
 HB=$!
-TIPS_BENCH_FAKE_HOSTS=1 timeout -k 10 ${N8_TIMEOUT:-1000} python -u bench.py --gpus 8 --steps 3 --warmup 1 \
+TIPS_BENCH_FAKE_HOSTS=1 timeout -k 10 ${N8_TIMEOUT:-1000} python -u bench.py --gpus 8 --full --steps 3 --warmup 1 \
   ${BENCH_ARGS:-} > "$OUT/rehearsal_n8.log" 2>&1
 rc=$?
 kill $HB

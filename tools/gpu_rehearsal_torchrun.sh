@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 ( while sleep 45; do date +%T >> "$OUT/heartbeat.txt"; done ) &
 HB=$!
 TIPS_BENCH_FAKE_HOSTS=1 timeout -k 10 ${REHEARSAL_TIMEOUT:-560} python -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus $N --steps 3 --warmup 1 \
+  --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus $N --full --steps 3 --warmup 1 \
   > "$OUT/rehearsal_n$N.log" 2>&1
 rc=$?
 kill $HB

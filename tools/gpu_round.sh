@@ -31,11 +31,11 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
   rc=$?; fatal $rc && exit $rc
 fi
-run bench 600 python bench.py ${BENCH_ARGS:-}
+run bench 600 python bench.py --full ${BENCH_ARGS:-}
 rc=$?; fatal $rc && exit $rc
 if [ "${EXTRA:-1}" = "1" ]; then
   for w in ${WORKLOADS:-bucket fused1000 resnet50 negotiated1000}; do
-    run bench_$w 300 python bench.py --workload $w --no-compare
+    run bench_$w 300 python bench.py --workload $w --full --no-compare
     rc=$?; fatal $rc && exit $rc
   done
 fi
