@@ -149,6 +149,41 @@ TIPS_API int tips_multi_sum(void* dst, const void* const* srcs, int nsrc, int64_
  * op must be TIPS_OP_SUM. */
 TIPS_API int tips_allreduce(const void* in, void* out, int64_t count, int dtype, int op, void* stream);
 
+/* ---- scaled forms: result = postscale * SUM over ranks of (prescale * x) ---- */
+
+/* One definition for every call below (Scaled allreduce). Every input element is
+ * multiplied by prescale exactly once, where a sum first reads it; every finished sum is multiplied
+ * by postscale exactly once, where it is written. The arithmetic runs in the working type - fp32
+ * for FLOAT32 / FLOAT16 / BFLOAT16, f64 for FLOAT64 - into which the factors are converted once on
+ * the host; every multiply and every add is a separate IEEE operation (never a fused multiply-add),
+ * and a kernel rounds to the storage type once, at its store. The factors sit inside the sum
+ * kernels, so a scaled call moves the bytes of the plain one. Float dtypes only: an integer dtype
+ * with a factor other than 1 returns TIPS_ERR_UNSUPPORTED; a factor that is not finite returns
+ * TIPS_ERR_INVALID_ARG. With both factors 1 each call is its plain twin, bit for bit. The factors
+ * must be the same on every rank (not validated). What the reference promises for
+ * allreduce(op=Average, prescale_factor=, postscale_factor=) and leaves commented out at its C++
+ * boundary (tips/tensorflow/__init__.py:82-87, :196). */
+
+/* dst[i] = src[i] * factor (rounded once), dst == src allowed. Device pointers, stream-ordered. */
+TIPS_API int tips_scale(void* dst, const void* src, int64_t count, int dtype, double factor, void* stream);
+/* dst[i] = (a[i] * prescale + b[i] * prescale) * postscale: tips_bucket_sum's launch with the
+ * factors inside it. In-place (dst == a or dst == b) allowed. */
+TIPS_API int tips_bucket_sum_scaled(void* dst, const void* a, const void* b, int64_t count, int dtype, double prescale,
+                                    double postscale, void* stream);
+/* dst[i] = (((srcs[0][i] * prescale) + (srcs[1][i] * prescale)) + ...) * postscale, in source order:
+ * tips_multi_sum's launch with the factors inside it, 1 <= nsrc <= 16. */
+TIPS_API int tips_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype,
+                                   double prescale, double postscale, void* stream);
+/* out = postscale * SUM over ranks of (prescale * in): tips_allreduce (device or host pointers, the
+ * pipelined host path included, in == out allowed) with the factors inside the schedule's sums - the
+ * ring multiplies each rank's chunk by prescale in the step that first adds it and by postscale in
+ * the step that completes it; direct and one-shot do both in their one fold. Under TIPS_ALGO_RCCL and
+ * TIPS_ALGO_PEER the factors are applied unfused (a scaled copy of in into out, the in-place
+ * allreduce, a scale of out). At one rank: the scaled copy. Routed through a running negotiation
+ * as an ALLREDUCE request, like tips_allreduce. Never captured or replayed as a graph (TIPS_GRAPHS). */
+TIPS_API int tips_allreduce_scaled(const void* in, void* out, int64_t count, int dtype, double prescale,
+                                   double postscale, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */
@@ -243,6 +278,11 @@ TIPS_API int64_t tips_fused_layout(const int64_t* counts, int n, int dtype, int6
  * unchanged; padding bytes of `flat` unspecified. One rank: one copy launch. Stream-ordered. */
 TIPS_API int tips_fused_allreduce_flat(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat,
                                        void* stream);
+/* tips_fused_allreduce_flat with the scale of tips_allreduce_scaled: the pack is unchanged and each
+ * bucket's in-place allreduce carries the factors; at one rank the pack is followed by one in-place
+ * scale of the flat buffer. What allreduce_grads(op=Average) runs under set_op_scaling. */
+TIPS_API int tips_fused_allreduce_flat_scaled(const void* const* ins, const int64_t* counts, int n, int dtype,
+                                              void* flat, double prescale, double postscale, void* stream);
 /* Measurement entry (bench.py, tools/copy_sweep_balanced.py): the pack launch the fusion issues for
  * bucket `bucket` of this list's layout (copy_segs_kernel over the bucket's tiles), into `dst` (device
  * memory of the bucket's padded size), on `stream`. Returns the bytes of the tensors the bucket holds

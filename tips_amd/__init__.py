@@ -11,6 +11,7 @@ from .compression import Compression, Compressor, FP16Compressor, NoneCompressor
 from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadcast_async, allreduce_async_many, synchronize_many, allreduce_op, broadcast_op, poll, synchronize, broadcast_variables, bucket_sum, fused_allreduce,
                   fused_allreduce_, rank_op, registered_host_buffer, set_algorithm, set_consistency_check, size_op)
 from .ops import fused_allreduce_cast, fused_allreduce_flat, fused_allreduce_host, fused_allreduce_host_flat, fusion_stats
+from .ops import set_op_scaling
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
@@ -36,7 +37,33 @@ __all__ = [
     "is_initialized", "size", "rank", "size_op", "rank_op", "set_algorithm", "Compression", "Compressor",
     "NoneCompressor", "FP16Compressor", "Average", "Sum", "TipsBasics", "TipsError", "TipsLibraryError",
     "DistributedOptimizer", "DistributedGradientTape", "fused_allreduce_cast", "fused_allreduce_flat", "fused_allreduce_host", "fused_allreduce_host_flat", "fusion_stats",
+    "allreduce_scaled", "set_op_scaling",
 ]
+
+
+def allreduce_scaled(tensor, prescale_factor=1.0, postscale_factor=1.0, name=None):
+    """postscale_factor * SUM over ranks of (prescale_factor * tensor): the scaled allreduce, whatever
+    set_op_scaling says (ops.allreduce_scaled_op: the factors sit inside the library's sum kernels;
+    with a `name` they are applied unfused around the named SUM). Float dtypes; the same factors on
+    every rank."""
+    return _ops.allreduce_scaled_op(tensor, prescale_factor, postscale_factor, name=name)
+
+
+def _op_scale(op, prescale_factor=1.0, postscale_factor=1.0):
+    """(prescale, postscale) a reduction runs with under set_op_scaling(True), or None for the plain
+    SUM (the switch is off, or nothing to scale): op=Average divides postscale by size(); op=Sum and
+    None sum, as the sparse branch treats them."""
+    if not _ops.op_scaling():
+        return None
+    pre, post = float(prescale_factor), float(postscale_factor)
+    if op == Average:
+        post = post / size()
+    return None if (pre == 1.0 and post == 1.0) else (pre, post)
+
+
+def _no_integer_average(tensor, op):
+    if op == Average and _ops.op_scaling() and _ops._is_integer(tensor):
+        raise ValueError("op=Average is not defined for integer tensors (dtype %s): reduce with op=Sum" % tensor.dtype)
 
 
 def allreduce(tensor,
@@ -50,12 +77,17 @@ def allreduce(tensor,
               name=None):
     """Sum `tensor` over all ranks — mirrors tips.tensorflow.allreduce (__init__.py:20-91).
 
-    Same arguments as the reference. As in the reference, `op`,
+    Same arguments as the reference. By default, as in the reference, `op`,
     `prescale_factor` and `postscale_factor` do not reach the reduction (they
     are commented out at the C++ boundary, __init__.py:82-87), so the result
     is the plain SUM for op=Average too — parity with the
-    reference, not a recommendation. `average`, `device_dense` and
-    `device_sparse` are accepted for signature compatibility.
+    reference, not a recommendation. After set_op_scaling(True) (or with
+    TIPS_OP_SCALING=1) they do: the result is postscale_factor * SUM over
+    ranks of (prescale_factor * tensor), op=Average dividing postscale_factor
+    by size() (op=Sum and None sum), computed by allreduce_scaled with the
+    factors inside the sum kernels; an integer tensor with op=Average raises
+    ValueError. `average`, `device_dense` and `device_sparse` are accepted for
+    signature compatibility.
 
     Sparse gradients take the reference's allgather branch (__init__.py:59-74).
     An `IndexedSlices` gets its values and indices allgathered, and they are
@@ -77,8 +109,13 @@ def allreduce(tensor,
         if op == Average:
             g_vals = g_vals / size()
         return torch.sparse_coo_tensor(g_idx, g_vals, tensor.shape)
+    _no_integer_average(tensor, op)
+    scale = _op_scale(op, prescale_factor, postscale_factor)
     tensor_compressed, ctx = compression.compress(tensor)
-    summed_tensor_compressed = allreduce_op(tensor_compressed, name=name)
+    if scale is not None:
+        summed_tensor_compressed = allreduce_scaled(tensor_compressed, scale[0], scale[1], name=name)
+    else:
+        summed_tensor_compressed = allreduce_op(tensor_compressed, name=name)
     return compression.decompress(summed_tensor_compressed, ctx)
 
 
@@ -109,7 +146,8 @@ def _to_dense(g):
     return g
 
 
-def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sparse_as_dense=False):
+def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sparse_as_dense=False,
+                    gradient_predivide_factor=1.0):
     """Allreduce a list of gradients (None entries pass through).
 
     Mirrors the per-gradient loop of _make_cached_allreduce_grads_fn
@@ -118,16 +156,29 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     gradients are densified first and then take the dense path). With
     fused=True, device tensors are summed through the fusion buckets (one
     allreduce per <=64 MiB bucket instead of one per gradient); outputs are
-    new tensors, inputs are left unchanged.
+    new tensors, inputs are left unchanged. Under set_op_scaling(True),
+    op=Average returns the average: the device lists through
+    tips_fused_allreduce_flat_scaled (postscale 1/size() inside each bucket's
+    sums); Compression.fp16 lists through the cast path followed by one
+    tips_scale per output buffer (unfused); host tensors one scaled allreduce
+    each. gradient_predivide_factor f (op=Average only) splits the division:
+    prescale 1/f before the sums, postscale f/size() after them.
     """
     if sparse_as_dense:
         grads = [_to_dense(g) if g is not None else g for g in grads]
     if size() <= 1:
         return list(grads)
-    return _reduce_grads(grads, compression, op, fused)
+    return _reduce_grads(grads, compression, op, fused, gradient_predivide_factor)
 
 
-def _reduce_grads(grads, compression=Compression.none, op=None, fused=True):
+def _average_scale(op, gradient_predivide_factor=1.0):
+    """_op_scale of a gradient reduction: op=Average with gradient_predivide_factor f is
+    prescale 1/f, postscale f/size()."""
+    f = float(gradient_predivide_factor)
+    return _op_scale(op, 1.0 / f, f) if op == Average else _op_scale(op)
+
+
+def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, gradient_predivide_factor=1.0):
     """What allreduce_grads runs at N > 1 (bench.py times it on one rank, where allreduce_grads
     itself is the identity). With fused=True:
       - dense device gradients, per dtype: fused_allreduce_flat - the outputs are views of one flat
@@ -143,6 +194,9 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True):
     if _DATA_PTR is None:
         import torch
         _DATA_PTR = torch.Tensor.data_ptr
+    scale = _average_scale(op, gradient_predivide_factor)
+    if scale is not None:
+        return _reduce_grads_scaled(grads, compression, scale, fused)
     if fused and grads and compression is FP16Compressor:  # (one list of dense f32 device tensors)
         res = _ops._dev_list_cast(grads)
         if res is not None:
@@ -214,6 +268,47 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True):
             out[i] = s if none else compression.decompress(s, ctx)
     if simple:
         _remember_plan(grads, plan_groups)
+    return out
+
+
+def _reduce_grads_scaled(grads, compression, scale, fused=True):
+    """_reduce_grads under set_op_scaling(True) with something to scale (op=Average at N > 1):
+    postscale * SUM(prescale * g) per gradient. Dense device gradients, per dtype, through
+    tips_fused_allreduce_flat_scaled - the factors inside each bucket's sums; float32 device
+    gradients under Compression.fp16 through the fused cast path, then one tips_scale per flat
+    output buffer (unfused); every other dense gradient (host tensors, other compressors) one
+    allreduce_scaled each; sparse ones through the allgather branch, which divides for Average."""
+    none = compression is Compression.none
+    if fused and none and grads:
+        res = _ops._dev_list_flat(grads, scale)  # (one dtype of dense device tensors: the common case)
+        if res is not None:
+            return res
+    out = list(grads)
+    dev, cast = {}, {}
+    for i, g in enumerate(grads):
+        if g is None:
+            continue
+        kind = _kind(g)
+        if kind is None:
+            out[i] = allreduce(g, compression=compression, op=Average)
+            continue
+        if _ops._is_integer(g):
+            raise ValueError("op=Average is not defined for integer gradients (dtype %s)" % g.dtype)
+        if fused and kind == "dev" and compression is FP16Compressor and g.dtype == _torch().float32:
+            cast.setdefault(g.device, []).append((i, g if g.is_contiguous() else g.contiguous()))
+        elif fused and kind == "dev" and none:
+            dev.setdefault((g.dtype, g.device), []).append((i, g if g.is_contiguous() else g.contiguous()))
+        else:
+            c, ctx = compression.compress(g)
+            out[i] = compression.decompress(allreduce_scaled(c, scale[0], scale[1]), ctx)
+    for members in dev.values():
+        ts = [c for _, c in members]
+        fo = _ops._flat_outputs(ts, _tensors.dtype_code(ts[0]))
+        for (i, _), s in zip(members, _ops._flat_run(fo, ts, list(map(_DATA_PTR, ts)), scale)):
+            out[i] = s
+    for members in cast.values():
+        for (i, _), s in zip(members, _ops.fused_allreduce_cast([c for _, c in members], "float16", scale)):
+            out[i] = s
     return out
 
 

@@ -77,6 +77,17 @@ _SIGNATURES = [
      [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     ("tips_allreduce", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    ("tips_scale", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
+    ("tips_bucket_sum_scaled", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+      ctypes.c_double, ctypes.c_void_p]),
+    ("tips_multi_sum_scaled", ctypes.c_int,
+     [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.c_void_p]),
+    ("tips_allreduce_scaled", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
@@ -95,6 +106,9 @@ _SIGNATURES = [
     ("tips_fused_layout", ctypes.c_int64, [_c_i64_p, ctypes.c_int, ctypes.c_int, _c_i64_p]),
     ("tips_fused_allreduce_flat", ctypes.c_int,
      [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tips_fused_allreduce_flat_scaled", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+      ctypes.c_void_p]),
     ("tips_fusion_stats", ctypes.c_int, [_c_i64_p, _c_i64_p, _c_i64_p, _c_i64_p]),
     ("tips_fused_pack_bucket", ctypes.c_int64,
      [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),

@@ -808,7 +808,10 @@ int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStre
 // flat = SUM over ranks of the inputs, tensor i at its layout offset: pack(b) straight into the
 // flat buffer's bucket b, allreduce it there in place. Every bucket has its own region, so all
 // packs go ahead on fuse_stream and allreduce(b) only waits for pack(b).
-int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t user) {
+// With a scale: each bucket's (and each large tensor's) allreduce carries it; at one rank the pack
+// is followed by one in-place scale of the whole flat buffer (its padding included).
+int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t user,
+                         const tips::Scale& sc) {
   if (n <= 0) return 0;
   FusionCache& fc = cache(st);
   const int64_t threshold = fusion_threshold_bytes();
@@ -826,13 +829,16 @@ int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, vo
     Table* t = find_table(st, fc, *L, kFlat, items, n, flat);
     if (!t) return TIPS_ERR_HIP;
     const int64_t es = tips::dtype_size(dtype);
-    const bool measure = st.size == 1 && env_i64("TIPS_FUSION_MEASURE_PACK", 0);
-    if (st.size == 1 && !measure)  // one rank: the identity - every tensor copied into place, one launch
-      return copy_tiles(*L, *t, 0, 0, L->ntiles, ws);
+    const bool measure = st.size == 1 && !sc.on() && env_i64("TIPS_FUSION_MEASURE_PACK", 0);
+    if (st.size == 1 && !measure) {  // one rank: the identity - every tensor copied into place, one launch
+      TRY(copy_tiles(*L, *t, 0, 0, L->ntiles, ws));
+      if (sc.on()) HIP_TRY(tips::launch_scale_buf(flat, flat, L->flat_bytes / es, dtype, sc.pre, sc.post, ws));
+      return 0;
+    }
     const int B = (int)L->buckets.size();
     hipStream_t red = st.size > 1 ? st.bucket_stream : ws;
     for (int i : L->direct)
-      TRY(allreduce_device(st, items[i].in, (char*)flat + L->off[i], items[i].count, dtype, red));
+      TRY(allreduce_device(st, items[i].in, (char*)flat + L->off[i], items[i].count, dtype, red, sc));
     TRY(st.fuse_ev.ensure((size_t)B));
     // merged: every bucket's pack in launches of up to kMaxPackGroups buckets, bucket order, each
     // bucket's allreduce behind its signal word (or, without signals, behind its launch)
@@ -851,7 +857,7 @@ int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, vo
         for (int k = 0; k < nb; k++) {
           if (signal) TRY(wait_packed(st, k, sigv[k]));
           char* p = (char*)flat + L->buckets[b0 + k].off;
-          TRY(allreduce_device(st, p, p, L->buckets[b0 + k].bytes / es, dtype, st.bucket_stream));
+          TRY(allreduce_device(st, p, p, L->buckets[b0 + k].bytes / es, dtype, st.bucket_stream, sc));
         }
       }
       b0 += nb;
@@ -1050,15 +1056,15 @@ int64_t tips_fused_layout(const int64_t* counts, int n, int dtype, int64_t* offs
   return fused_layout(counts, n, dtype, offsets);
 }
 
-int tips_fused_allreduce_flat(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat,
-                              void* stream) {
+static int fused_flat_entry(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat, void* stream,
+                            const tips::Scale& sc) {
   std::vector<BatchItem> items;
   TRY(check_list(ins, counts, n, dtype, &items, nullptr));
   int routed_rc;
   int64_t shape[2];
   list_shape(counts, n, shape);
   if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 2, 0,
-                       [&] { return tips_fused_allreduce_flat(ins, counts, n, dtype, flat, stream); }, &routed_rc))
+                       [&] { return fused_flat_entry(ins, counts, n, dtype, flat, stream, sc); }, &routed_rc))
     return routed_rc;
   State& st = S();
   std::lock_guard<std::mutex> lk(st.mu);
@@ -1068,7 +1074,19 @@ int tips_fused_allreduce_flat(const void* const* ins, const int64_t* counts, int
   TRY(set_device(st));
   if (!is_device_ptr(flat)) return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_flat needs device memory");
   for (auto& it : items) it.out = it.count ? flat : nullptr;
-  return fused_allreduce_flat(st, items.data(), n, dtype, flat, (hipStream_t)stream);
+  return fused_allreduce_flat(st, items.data(), n, dtype, flat, (hipStream_t)stream, sc);
+}
+
+int tips_fused_allreduce_flat(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat,
+                              void* stream) {
+  return fused_flat_entry(ins, counts, n, dtype, flat, stream, tips::Scale());
+}
+
+int tips_fused_allreduce_flat_scaled(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat,
+                                     double prescale, double postscale, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_scale(dtype, prescale, postscale));
+  return fused_flat_entry(ins, counts, n, dtype, flat, stream, tips::Scale{prescale, postscale});
 }
 
 int64_t tips_fused_pack_bucket(const void* const* ins, const int64_t* counts, int n, int dtype, int bucket, void* dst,

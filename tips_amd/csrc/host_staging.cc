@@ -34,7 +34,7 @@ int ensure_bounce(State& st) {
 // stages; otherwise a second host thread issues the D2H copies, because a
 // copy from/to pageable memory blocks the thread that issues it. Caller holds
 // st.mu; returns when `out` is written.
-int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, int dtype) {
+int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, int dtype, const tips::Scale& sc) {
   const int64_t es = tips::dtype_size(dtype);
   const int64_t piece =
       round_up(std::max<int64_t>(kAlignBytes, env_i64("TIPS_HOST_PIECE_BYTES", kHostPieceBytes)), kAlignBytes) / es;
@@ -50,7 +50,7 @@ int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, in
       HIP_TRY(hipMemcpyAsync(din + off, in + off, (size_t)(cnt * es), hipMemcpyHostToDevice, st.h2d_stream));
       HIP_TRY(hipEventRecord(st.pipe_ev.ev[2 * i], st.h2d_stream));
       HIP_TRY(hipStreamWaitEvent(st.io_stream, st.pipe_ev.ev[2 * i], 0));
-      TRY(allreduce_device(st, din + off, dout + off, cnt, dtype, st.io_stream));
+      TRY(allreduce_device(st, din + off, dout + off, cnt, dtype, st.io_stream, sc));
       HIP_TRY(hipEventRecord(st.pipe_ev.ev[2 * i + 1], st.io_stream));
       HIP_TRY(hipStreamWaitEvent(st.d2h_stream, st.pipe_ev.ev[2 * i + 1], 0));
       HIP_TRY(hipMemcpyAsync(out + off, dout + off, (size_t)(cnt * es), hipMemcpyDeviceToHost, st.d2h_stream));
@@ -92,7 +92,7 @@ int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, in
       rc = fail(TIPS_ERR_HIP, "H2D piece %d: %s", i, hipGetErrorString(e));
       break;
     }
-    rc = allreduce_device(st, din + off, dout + off, cnt, dtype, st.io_stream);
+    rc = allreduce_device(st, din + off, dout + off, cnt, dtype, st.io_stream, sc);
     if (rc == 0 && (e = hipEventRecord(st.pipe_ev.ev[2 * i + 1], st.io_stream)) != hipSuccess)
       rc = fail(TIPS_ERR_HIP, "event: %s", hipGetErrorString(e));
     if (rc == 0) {

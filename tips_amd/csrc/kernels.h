@@ -22,6 +22,23 @@ hipError_t launch_multi_sum(void* dst, const void* const* srcs, int nsrc, int64_
 // (256 lanes, 16 KiB per source per workgroup, no occupancy cap). Same bits as launch_multi_sum.
 hipError_t launch_multi_sum_remote(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, hipStream_t s);
 
+// Scaled forms (float dtypes; DESIGN.md §Scaled allreduce): result = post * SUM (pre * x), in the
+// working type (fp32 for f32 / f16 / bf16, f64 for f64), every multiply and add a separate IEEE
+// operation, one rounding at the store. Bit j of `raw` marks source j as a rank's raw input, to be
+// multiplied by pre where it is read; the other sources are partial sums that already carry it. The
+// launch shapes are those of launch_sum2 / launch_multi_sum / launch_copy_buf; with nothing to scale
+// (pre == 1 or no raw source, and post == 1) they are those launchers.
+struct Scale {
+  double pre = 1.0, post = 1.0;
+  bool on() const { return pre != 1.0 || post != 1.0; }
+};
+hipError_t launch_sum2_scaled(void* dst, const void* a, const void* b, int64_t n, int dtype, double pre, double post,
+                              unsigned raw, hipStream_t s);
+hipError_t launch_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, double pre,
+                                   double post, unsigned raw, hipStream_t s);
+// dst = (src * pre) * post over n elements, in place allowed (tips_scale; the scaled allreduce at one rank).
+hipError_t launch_scale_buf(void* dst, const void* src, int64_t n, int dtype, double pre, double post, hipStream_t s);
+
 // Batched byte copy for fusion pack/unpack: one workgroup per tile.
 struct CopyTile {
   const char* src;

@@ -149,6 +149,216 @@ __device__ __forceinline__ void add_elem<kBF16>(void* d, const void* a, const vo
   ((unsigned short*)d)[i] = (unsigned short)bf16_round_bits(__builtin_bit_cast(unsigned, s));
 }
 
+// The accumulation type of a 16-byte vector per dtype (the multi-input fold and the scaled forms):
+// f16/bf16 widen to fp32 and round once at the store; the others stay in their storage type.
+template <int DT>
+struct Wide;
+template <>
+struct Wide<kF32> {
+  using A = f32x4;
+  static __device__ A load(u32x4 v) { return __builtin_bit_cast(f32x4, v); }
+  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
+};
+template <>
+struct Wide<kF64> {
+  using A = f64x2;
+  static __device__ A load(u32x4 v) { return __builtin_bit_cast(f64x2, v); }
+  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
+};
+template <>
+struct Wide<kI32> {
+  using A = u32x4;
+  static __device__ A load(u32x4 v) { return v; }
+  static __device__ u32x4 store(A a) { return a; }
+};
+template <>
+struct Wide<kI64> {
+  using A = u64x2;
+  static __device__ A load(u32x4 v) { return __builtin_bit_cast(u64x2, v); }
+  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
+};
+template <>
+struct Wide<kF16> {
+  using A = f32x8;
+  static __device__ A load(u32x4 v) { return __builtin_convertvector(__builtin_bit_cast(f16x8, v), f32x8); }
+  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, __builtin_convertvector(a, f16x8)); }
+};
+template <>
+struct Wide<kBF16> {
+  using A = f32x8;
+  static __device__ A load(u32x4 v) {
+    f32x4 lo = bf16_lo(v), hi = bf16_hi(v);
+    return A{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  }
+  static __device__ u32x4 store(A a) {
+    return bf16_pack(f32x4{a[0], a[1], a[2], a[3]}, f32x4{a[4], a[5], a[6], a[7]});
+  }
+};
+
+template <int DT>
+struct ScalarOf;
+template <>
+struct ScalarOf<kF32> {
+  using T = float;
+};
+template <>
+struct ScalarOf<kF64> {
+  using T = double;
+};
+template <>
+struct ScalarOf<kI32> {
+  using T = unsigned;
+};
+template <>
+struct ScalarOf<kI64> {
+  using T = unsigned long long;
+};
+template <>
+struct ScalarOf<kF16> {
+  using T = _Float16;
+};
+template <>
+struct ScalarOf<kBF16> {
+  using T = unsigned short;
+};
+
+// ---------------------------------------------------------------------------
+// Scaled forms (DESIGN.md §Scaled allreduce): result = post * SUM_r (pre * x_r). The sum, fold and
+// copy kernels below take an optional trailing ScaleArgs<DT>; without it they are the plain kernels,
+// instruction for instruction. With it every operand whose bit of `raw` is set is multiplied by pre
+// where it is read, the operands are added in source order, the sum is multiplied by post, and the
+// result is rounded to the storage type once, at the store. All of it in the working type W (fp32
+// for f32 / f16 / bf16, f64 for f64), every multiply and add its own IEEE operation: contraction
+// is off in these helpers, or a*s + b*s would become a fused multiply-add. An operand that is not raw
+// (a partial sum a peer already scaled) and a sum that is not final (post = 1) are multiplied by 1,
+// which changes no bit. Float dtypes only.
+template <int DT>
+struct WorkOf {
+  using T = float;
+};
+template <>
+struct WorkOf<kF64> {
+  using T = double;
+};
+
+template <int DT>
+struct ScaleArgs {
+  typename WorkOf<DT>::T pre, post;
+  unsigned raw;  // bit j: source j is a rank's raw input (not yet multiplied by pre)
+  __device__ __forceinline__ typename WorkOf<DT>::T in(int j) const { return ((raw >> j) & 1u) ? pre : 1; }
+};
+
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A scaled_load(u32x4 v, typename WorkOf<DT>::T f) {
+#pragma clang fp contract(off)
+  return Wide<DT>::load(v) * f;
+}
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A separate_add(typename Wide<DT>::A a, typename Wide<DT>::A b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+template <int DT>
+__device__ __forceinline__ u32x4 scaled_store(typename Wide<DT>::A a, typename WorkOf<DT>::T f) {
+#pragma clang fp contract(off)
+  return Wide<DT>::store(a * f);
+}
+
+// one element in W, and its single rounding back to the storage type
+template <int DT>
+__device__ __forceinline__ typename WorkOf<DT>::T load_work(const void* p, int64_t i) {
+  if constexpr (DT == kBF16) return __builtin_bit_cast(float, (unsigned)((const unsigned short*)p)[i] << 16);
+  else return (typename WorkOf<DT>::T)((const typename ScalarOf<DT>::T*)p)[i];
+}
+template <int DT>
+__device__ __forceinline__ void store_work(void* p, int64_t i, typename WorkOf<DT>::T v) {
+  if constexpr (DT == kBF16) ((unsigned short*)p)[i] = (unsigned short)bf16_round_bits(__builtin_bit_cast(unsigned, v));
+  else if constexpr (DT == kF16) {
+    // the fp32 product is a value of its own before it is rounded to half: without this the compiler
+    // folds the last multiply and the conversion into one v_fma_mixlo_f16, which the vector path
+    // (v_pk_mul_f32, then v_cvt_pk_f16_f32) does not do - tails and the scalar fallback must match it
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    ((_Float16*)p)[i] = (_Float16)v;
+  } else ((typename ScalarOf<DT>::T*)p)[i] = (typename ScalarOf<DT>::T)v;
+}
+
+// dst[i] = (((s0 * f0) + (s1 * f1)) + ...) * post for one element (tails and the unaligned fallback)
+template <int DT>
+__device__ __forceinline__ void fold_elem(void* dst, const void* const* srcs, int nsrc, int64_t i, ScaleArgs<DT> sc) {
+#pragma clang fp contract(off)
+  typename WorkOf<DT>::T acc = load_work<DT>(srcs[0], i) * sc.in(0);
+  for (int j = 1; j < nsrc; j++) {
+    const typename WorkOf<DT>::T x = load_work<DT>(srcs[j], i) * sc.in(j);
+    acc = acc + x;
+  }
+  store_work<DT>(dst, i, acc * sc.post);
+}
+
+// the 2-input sum's vector and element: plain, or scaled
+template <int DT>
+__device__ __forceinline__ u32x4 sum16(u32x4 a, u32x4 b) {
+  return add16<DT>(a, b);
+}
+template <int DT>
+__device__ __forceinline__ u32x4 sum16(u32x4 a, u32x4 b, ScaleArgs<DT> sc) {
+  return scaled_store<DT>(separate_add<DT>(scaled_load<DT>(a, sc.in(0)), scaled_load<DT>(b, sc.in(1))), sc.post);
+}
+template <int DT>
+__device__ __forceinline__ void sum_elem(void* dst, const void* a, const void* b, int64_t i) {
+  add_elem<DT>(dst, a, b, i);
+}
+template <int DT>
+__device__ __forceinline__ void sum_elem(void* dst, const void* a, const void* b, int64_t i, ScaleArgs<DT> sc) {
+  const void* s[2] = {a, b};
+  fold_elem<DT>(dst, s, 2, i, sc);
+}
+
+// the fold's steps: plain, or scaled
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A fold_first(u32x4 v) {
+  return Wide<DT>::load(v);
+}
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A fold_first(u32x4 v, ScaleArgs<DT> sc) {
+  return scaled_load<DT>(v, sc.in(0));
+}
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A fold_next(typename Wide<DT>::A acc, u32x4 v, int) {
+  return acc + Wide<DT>::load(v);
+}
+template <int DT>
+__device__ __forceinline__ typename Wide<DT>::A fold_next(typename Wide<DT>::A acc, u32x4 v, int j, ScaleArgs<DT> sc) {
+  return separate_add<DT>(acc, scaled_load<DT>(v, sc.in(j)));
+}
+template <int DT>
+__device__ __forceinline__ u32x4 fold_store(typename Wide<DT>::A acc) {
+  return Wide<DT>::store(acc);
+}
+template <int DT>
+__device__ __forceinline__ u32x4 fold_store(typename Wide<DT>::A acc, ScaleArgs<DT> sc) {
+  return scaled_store<DT>(acc, sc.post);
+}
+
+// the contiguous copy's vector and trailing bytes: plain, or scaled (source 0 is raw)
+__device__ __forceinline__ u32x4 copy16(u32x4 v) { return v; }
+template <int DT>
+__device__ __forceinline__ u32x4 copy16(u32x4 v, ScaleArgs<DT> sc) {
+  return scaled_store<DT>(scaled_load<DT>(v, sc.in(0)), sc.post);
+}
+__device__ __forceinline__ void copy_tail(void* dst, const void* src, int64_t tail_begin, int64_t bytes, int tid) {
+  if (tail_begin + tid < bytes)
+    reinterpret_cast<char*>(dst)[tail_begin + tid] = reinterpret_cast<const char*>(src)[tail_begin + tid];
+}
+template <int DT>
+__device__ __forceinline__ void copy_tail(void* dst, const void* src, int64_t tail_begin, int64_t bytes, int tid,
+                                          ScaleArgs<DT> sc) {
+  constexpr int64_t es = sizeof(typename ScalarOf<DT>::T);
+  const int64_t i = tail_begin / es + tid;
+  if (i < bytes / es) fold_elem<DT>(dst, &src, 1, i, sc);
+}
+
 // XCD-contiguous tile order: workgroups are dealt round-robin over the 8 XCDs
 // (b and b+8 share one), so tile = (b % 8) * (grid / 8) + b / 8 hands each XCD
 // one contiguous stretch. Needs grid % 8 == 0; speed only, never correctness.
@@ -213,10 +423,11 @@ __global__ __launch_bounds__(BLOCK) void sum2_kernel(u32x4* __restrict__ dst, co
 // 512 KiB stripes (round 6; rounds 2-5: 256 lanes with sc1 stores, which won when one buffer
 // triple was re-read, 7.46 vs 7.10 TB/s, profiles/r01_sum_sweep_f.jsonl). Each workgroup's
 // descriptors cover exactly its tile, so the hardware range check drops lanes past the end.
-template <int DT, int LAUX, int SAUX, int U = 1, int BLOCK = 256>
+// SC: empty (the plain sum), or one ScaleArgs<DT> (the scaled sum, see "Scaled forms" above).
+template <int DT, int LAUX, int SAUX, int U = 1, int BLOCK = 256, class... SC>
 __global__ __launch_bounds__(BLOCK) void sum2_buf_kernel(u32x4* __restrict__ dst, const u32x4* __restrict__ a,
                                                         const u32x4* __restrict__ b, int64_t nvec,
-                                                        int64_t tail_begin, int64_t n, int64_t stripe) {
+                                                        int64_t tail_begin, int64_t n, int64_t stripe, SC... sc) {
   constexpr int64_t kTile = (int64_t)BLOCK * U;
   const int64_t t = stripe_tile(blockIdx.x, gridDim.x, stripe);
   const int64_t first = t * kTile;
@@ -232,9 +443,9 @@ __global__ __launch_bounds__(BLOCK) void sum2_buf_kernel(u32x4* __restrict__ dst
     for (int u = 0; u < U; u++) y[u] = __builtin_amdgcn_raw_buffer_load_b128(rb, (u * BLOCK + (int)threadIdx.x) * 16, 0, LAUX);
 #pragma unroll
     for (int u = 0; u < U; u++)
-      __builtin_amdgcn_raw_buffer_store_b128(add16<DT>(x[u], y[u]), rd, (u * BLOCK + (int)threadIdx.x) * 16, 0, SAUX);
+      __builtin_amdgcn_raw_buffer_store_b128(sum16<DT>(x[u], y[u], sc...), rd, (u * BLOCK + (int)threadIdx.x) * 16, 0, SAUX);
   }
-  if (blockIdx.x == 0 && tail_begin + (int64_t)threadIdx.x < n) add_elem<DT>(dst, a, b, tail_begin + threadIdx.x);
+  if (blockIdx.x == 0 && tail_begin + (int64_t)threadIdx.x < n) sum_elem<DT>(dst, a, b, tail_begin + threadIdx.x, sc...);
 }
 
 // The shipped sum with other workgroup -> tile maps (tuning sweep only, f32; the 128 MiB dip,
@@ -349,86 +560,15 @@ __global__ __launch_bounds__(256) void sum2_stream_kernel(u32x4* __restrict__ ds
 #endif  // TIPS_DEV
 
 // Unaligned fallback (any pointer not 16-B aligned): one element per lane.
-template <int DT>
-__global__ __launch_bounds__(kBlock) void sum2_scalar_kernel(void* dst, const void* a, const void* b, int64_t n) {
+template <int DT, class... SC>
+__global__ __launch_bounds__(kBlock) void sum2_scalar_kernel(void* dst, const void* a, const void* b, int64_t n, SC... sc) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    add_elem<DT>(dst, a, b, i);
+    sum_elem<DT>(dst, a, b, i, sc...);
 }
 
 // ---------------------------------------------------------------------------
 // Multi-input sum: dst = ((s0 + s1) + s2) + ...  (rank-order fold)
 // f16/bf16 accumulate in fp32 and round once; others accumulate in storage type.
-
-template <int DT>
-struct Wide;
-template <>
-struct Wide<kF32> {
-  using A = f32x4;
-  static __device__ A load(u32x4 v) { return __builtin_bit_cast(f32x4, v); }
-  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
-};
-template <>
-struct Wide<kF64> {
-  using A = f64x2;
-  static __device__ A load(u32x4 v) { return __builtin_bit_cast(f64x2, v); }
-  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
-};
-template <>
-struct Wide<kI32> {
-  using A = u32x4;
-  static __device__ A load(u32x4 v) { return v; }
-  static __device__ u32x4 store(A a) { return a; }
-};
-template <>
-struct Wide<kI64> {
-  using A = u64x2;
-  static __device__ A load(u32x4 v) { return __builtin_bit_cast(u64x2, v); }
-  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, a); }
-};
-template <>
-struct Wide<kF16> {
-  using A = f32x8;
-  static __device__ A load(u32x4 v) { return __builtin_convertvector(__builtin_bit_cast(f16x8, v), f32x8); }
-  static __device__ u32x4 store(A a) { return __builtin_bit_cast(u32x4, __builtin_convertvector(a, f16x8)); }
-};
-template <>
-struct Wide<kBF16> {
-  using A = f32x8;
-  static __device__ A load(u32x4 v) {
-    f32x4 lo = bf16_lo(v), hi = bf16_hi(v);
-    return A{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  }
-  static __device__ u32x4 store(A a) {
-    return bf16_pack(f32x4{a[0], a[1], a[2], a[3]}, f32x4{a[4], a[5], a[6], a[7]});
-  }
-};
-
-template <int DT>
-struct ScalarOf;
-template <>
-struct ScalarOf<kF32> {
-  using T = float;
-};
-template <>
-struct ScalarOf<kF64> {
-  using T = double;
-};
-template <>
-struct ScalarOf<kI32> {
-  using T = unsigned;
-};
-template <>
-struct ScalarOf<kI64> {
-  using T = unsigned long long;
-};
-template <>
-struct ScalarOf<kF16> {
-  using T = _Float16;
-};
-template <>
-struct ScalarOf<kBF16> {
-  using T = unsigned short;
-};
 
 template <int DT>
 __device__ __forceinline__ void fold_elem(void* dst, const void* const* srcs, int nsrc, int64_t i) {
@@ -489,9 +629,10 @@ __global__ __launch_bounds__(kBlock) void multi_sum_kernel(u32x4* __restrict__ d
 // Buffer-op form of the multi-input sum: one descriptor per source covering
 // this workgroup's tile, cache-policy bits on the loads (LAUX) and sc1 stores,
 // every source's vectors in flight before the fold (as sum2_buf_kernel).
-template <int DT, int NSRC, int U, int LAUX, int BLOCK = kBlock, int SAUX = 16>
+// SC: empty (the plain fold), or one ScaleArgs<DT> (the scaled fold).
+template <int DT, int NSRC, int U, int LAUX, int BLOCK = kBlock, int SAUX = 16, class... SC>
 __global__ __launch_bounds__(BLOCK) void multi_sum_buf_kernel(u32x4* __restrict__ dst, SrcList srcs, int64_t nvec,
-                                                             int64_t tail_begin, int64_t n, int64_t stripe) {
+                                                             int64_t tail_begin, int64_t n, int64_t stripe, SC... sc) {
   using W = Wide<DT>;
   constexpr int64_t kTile = (int64_t)BLOCK * U;
   const int tid = threadIdx.x;
@@ -508,17 +649,17 @@ __global__ __launch_bounds__(BLOCK) void multi_sum_buf_kernel(u32x4* __restrict_
     __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void*)(dst + first), (short)0, rec, 0x00020000);
 #pragma unroll
     for (int u = 0; u < U; u++) {
-      typename W::A acc = W::load(v[u][0]);
+      typename W::A acc = fold_first<DT>(v[u][0], sc...);
 #pragma unroll
-      for (int j = 1; j < NSRC; j++) acc = acc + W::load(v[u][j]);
-      __builtin_amdgcn_raw_buffer_store_b128(W::store(acc), rd, (u * BLOCK + tid) * 16, 0, SAUX);
+      for (int j = 1; j < NSRC; j++) acc = fold_next<DT>(acc, v[u][j], j, sc...);
+      __builtin_amdgcn_raw_buffer_store_b128(fold_store<DT>(acc, sc...), rd, (u * BLOCK + tid) * 16, 0, SAUX);
     }
   }
   if (blockIdx.x == 0 && NSRC > 1 && tail_begin + tid < n) {
     const void* s[NSRC];
 #pragma unroll
     for (int j = 0; j < NSRC; j++) s[j] = srcs.p[j];
-    fold_elem<DT>(dst, s, NSRC, tail_begin + tid);
+    fold_elem<DT>(dst, s, NSRC, tail_begin + tid, sc...);
   }
 }
 
@@ -640,12 +781,12 @@ __global__ __launch_bounds__(BLOCK) void multi_sum_gs_kernel(u32x4* __restrict__
 }
 #endif  // TIPS_DEV
 
-template <int DT>
-__global__ __launch_bounds__(kBlock) void multi_sum_scalar_kernel(void* dst, SrcList srcs, int nsrc, int64_t n) {
+template <int DT, class... SC>
+__global__ __launch_bounds__(kBlock) void multi_sum_scalar_kernel(void* dst, SrcList srcs, int nsrc, int64_t n, SC... sc) {
   const void* s[kMaxSrcs];
   for (int j = 0; j < nsrc; j++) s[j] = srcs.p[j];
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
-    fold_elem<DT>(dst, s, nsrc, i);
+    fold_elem<DT>(dst, s, nsrc, i, sc...);
 }
 
 // ---------------------------------------------------------------------------
@@ -725,9 +866,12 @@ __global__ __launch_bounds__(kBlock) void copy_tiles_g_kernel(const CopyTile* __
 // order, buffer loads nt, buffer stores sc1 (the line leaves the XCD's L2), descriptors covering
 // exactly the tile; the < 16 trailing bytes go bytewise in workgroup 0. (hipMemcpyAsync's D2D blit
 // moved config 3's 1 GiB at 0.62 of HBM, profiles/r04/n_bench_n1.jsonl.)
-template <int U, int SAUX = 16, int BLOCK = kBlock>
+// SC: empty (the copy), or one ScaleArgs<DT>: dst = (src * pre) * post (in place allowed: every lane
+// stores only what it loaded), the trailing elements by workgroup 0 one per lane.
+template <int U, int SAUX = 16, int BLOCK = kBlock, class... SC>
 __global__ __launch_bounds__(BLOCK) void copy_buf_kernel(u32x4* __restrict__ dst, const u32x4* __restrict__ src,
-                                                         int64_t nvec, int64_t tail_begin, int64_t bytes, int64_t stripe) {
+                                                         int64_t nvec, int64_t tail_begin, int64_t bytes, int64_t stripe,
+                                                         SC... sc) {
   constexpr int64_t kTile = (int64_t)BLOCK * U;
   const int64_t first = stripe_tile(blockIdx.x, gridDim.x, stripe) * kTile;
   const int tid = threadIdx.x;
@@ -739,10 +883,10 @@ __global__ __launch_bounds__(BLOCK) void copy_buf_kernel(u32x4* __restrict__ dst
 #pragma unroll
     for (int u = 0; u < U; u++) v[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (u * BLOCK + tid) * 16, 0, 2);
 #pragma unroll
-    for (int u = 0; u < U; u++) __builtin_amdgcn_raw_buffer_store_b128(v[u], rd, (u * BLOCK + tid) * 16, 0, SAUX);
+    for (int u = 0; u < U; u++)
+      __builtin_amdgcn_raw_buffer_store_b128(copy16(v[u], sc...), rd, (u * BLOCK + tid) * 16, 0, SAUX);
   }
-  if (blockIdx.x == 0 && tail_begin + tid < bytes)
-    reinterpret_cast<char*>(dst)[tail_begin + tid] = reinterpret_cast<const char*>(src)[tail_begin + tid];
+  if (blockIdx.x == 0) copy_tail(dst, src, tail_begin, bytes, tid, sc...);
 }
 
 // Stripe size for stripe_tile, in 16-B vectors of one operand (TIPS_STRIPE_KIB, default 1 MiB;
@@ -833,6 +977,42 @@ hipError_t launch_copy_buf(void* dst, const void* src, int64_t bytes, hipStream_
   else
     hipLaunchKernelGGL((copy_buf_kernel<1>), g, b, 0, s, (u32x4*)dst, (const u32x4*)src, nvec, nvec * 16, bytes, stripe);
   return hipGetLastError();
+}
+
+// The scaled copy, dst = (src * pre) * post over n elements (tips_scale, and the scaled allreduce at
+// one rank): launch_copy_buf's shipped shape (4 KiB tiles, nt loads, sc1 stores, 1 MiB stripes) with
+// the multiplies between load and store; pointers that are not 16-B aligned take the scalar fold.
+template <int DT>
+hipError_t scale_buf_dispatch(void* dst, const void* src, int64_t n, double pre, double post, hipStream_t s) {
+  using T = typename WorkOf<DT>::T;
+  const ScaleArgs<DT> sc{(T)pre, (T)post, 1u};
+  if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) != 0) {
+    SrcList sl{};
+    sl.p[0] = (const u32x4*)src;
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, 256 * 16));
+    hipLaunchKernelGGL((multi_sum_scalar_kernel<DT, ScaleArgs<DT>>), dim3((unsigned)grid), dim3(kBlock), 0, s, dst, sl, 1,
+                       n, sc);
+    return hipGetLastError();
+  }
+  const int64_t bytes = n * dtype_size(DT), nvec = bytes / 16;
+  const int64_t stripe = stripe_of(kBlock);
+  const int64_t grid = stripe_grid((nvec + kBlock - 1) / kBlock, stripe);
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((copy_buf_kernel<1, 16, kBlock, ScaleArgs<DT>>), dim3((unsigned)grid), dim3(kBlock), 0, s,
+                     (u32x4*)dst, (const u32x4*)src, nvec, nvec * 16, bytes, stripe, sc);
+  return hipGetLastError();
+}
+
+hipError_t launch_scale_buf(void* dst, const void* src, int64_t n, int dtype, double pre, double post, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (pre == 1.0 && post == 1.0) return launch_copy_buf(dst, src, n * dtype_size(dtype), s);
+  switch (dtype) {
+    case kF32: return scale_buf_dispatch<kF32>(dst, src, n, pre, post, s);
+    case kF64: return scale_buf_dispatch<kF64>(dst, src, n, pre, post, s);
+    case kF16: return scale_buf_dispatch<kF16>(dst, src, n, pre, post, s);
+    case kBF16: return scale_buf_dispatch<kBF16>(dst, src, n, pre, post, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1503,8 +1683,9 @@ inline bool fold_store_nt() {
   return v;
 }
 
-template <int DT, int NSRC>
-hipError_t run_multi(void* dst, const SrcList& sl, int64_t n, hipStream_t s) {
+// (sc: empty, or the scaled fold's ScaleArgs<DT> - the same launch shapes either way)
+template <int DT, int NSRC, class... SC>
+hipError_t run_multi(void* dst, const SrcList& sl, int64_t n, hipStream_t s, SC... sc) {
   // buffer loads, non-temporal for every source count. Round 1 kept plain loads beyond 4 sources
   // from a sweep that re-read one buffer set (plain 44.7 vs nt 47.3 us, 8 x 32 MiB, Infinity Cache
   // assisted); with operands from HBM, as the direct schedule's fold mostly reads them, nt wins
@@ -1524,17 +1705,17 @@ hipError_t run_multi(void* dst, const SrcList& sl, int64_t n, hipStream_t s) {
   const int64_t grid = stripe_grid((nvec + per - 1) / per, stripe);  // surplus workgroups fall off the bounds check
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   if (capped && fold_store_nt())
-    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX, kCapBlock, 2>), dim3((unsigned)grid), dim3(kCapBlock),
-                       NSRC >= 6 ? kFoldLdsCap5 : kFoldLdsCap8, s, (u32x4*)dst, sl, nvec, nvec * ve, n, stripe);
+    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX, kCapBlock, 2, SC...>), dim3((unsigned)grid), dim3(kCapBlock),
+                       NSRC >= 6 ? kFoldLdsCap5 : kFoldLdsCap8, s, (u32x4*)dst, sl, nvec, nvec * ve, n, stripe, sc...);
   else if (capped)
-    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX, kCapBlock>), dim3((unsigned)grid), dim3(kCapBlock),
-                       NSRC >= 6 ? kFoldLdsCap5 : kFoldLdsCap8, s, (u32x4*)dst, sl, nvec, nvec * ve, n, stripe);
+    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX, kCapBlock, 16, SC...>), dim3((unsigned)grid), dim3(kCapBlock),
+                       NSRC >= 6 ? kFoldLdsCap5 : kFoldLdsCap8, s, (u32x4*)dst, sl, nvec, nvec * ve, n, stripe, sc...);
   else if (u4)
-    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 4, LAUX>), dim3((unsigned)grid), dim3(kBlock), 0, s,
-                       (u32x4*)dst, sl, nvec, nvec * ve, n, stripe);
+    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 4, LAUX, kBlock, 16, SC...>), dim3((unsigned)grid), dim3(kBlock), 0, s,
+                       (u32x4*)dst, sl, nvec, nvec * ve, n, stripe, sc...);
   else
-    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX>), dim3((unsigned)grid), dim3(kBlock), 0, s,
-                       (u32x4*)dst, sl, nvec, nvec * ve, n, stripe);
+    hipLaunchKernelGGL((multi_sum_buf_kernel<DT, NSRC, 1, LAUX, kBlock, 16, SC...>), dim3((unsigned)grid), dim3(kBlock), 0, s,
+                       (u32x4*)dst, sl, nvec, nvec * ve, n, stripe, sc...);
   return hipGetLastError();
 }
 
@@ -1691,8 +1872,29 @@ hipError_t run_multi_remote(void* dst, const SrcList& sl, int64_t n, hipStream_t
   return hipGetLastError();
 }
 
+// The scaled 2-input sum: the product launch of sum2_dispatch (kDef*: 128 lanes, one 16-B vector per
+// lane per operand, nt loads and stores, 512 KiB stripes) with ScaleArgs; scalar kernel when unaligned.
 template <int DT>
-hipError_t multi_dispatch(void* dst, const void* const* srcs, int nsrc, int64_t n, hipStream_t s, bool remote = false) {
+hipError_t sum2_scaled_dispatch(void* dst, const void* a, const void* b, int64_t n, ScaleArgs<DT> sc, hipStream_t s) {
+  if (!(aligned16(dst) && aligned16(a) && aligned16(b))) {
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kNumCUs * 16));
+    hipLaunchKernelGGL((sum2_scalar_kernel<DT, ScaleArgs<DT>>), dim3((unsigned)grid), dim3(kBlock), 0, s, dst, a, b, n, sc);
+    return hipGetLastError();
+  }
+  static_assert(kDefMode == 3 && kDefNT == 7, "the scaled sum restates the product default's buffer-op case");
+  constexpr int64_t kTile = (int64_t)kDefUnroll * kDefThreads;
+  const int64_t ve = 16 / (int64_t)dtype_size(DT);
+  const int64_t nvec = n / ve;
+  const int64_t grid = stripe_grid((nvec + kTile - 1) / kTile, sum_stripe_of(kTile));
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((sum2_buf_kernel<DT, 2, 2, kDefUnroll, kDefThreads, ScaleArgs<DT>>), dim3((unsigned)grid),
+                     dim3(kDefThreads), 0, s, (u32x4*)dst, (const u32x4*)a, (const u32x4*)b, nvec, nvec * ve, n,
+                     sum_stripe_of(kTile), sc);
+  return hipGetLastError();
+}
+
+template <int DT, class... SC>
+hipError_t multi_dispatch(void* dst, const void* const* srcs, int nsrc, int64_t n, hipStream_t s, bool remote, SC... sc) {
   SrcList sl{};
   bool al = aligned16(dst);
   for (int j = 0; j < nsrc; j++) {
@@ -1703,14 +1905,17 @@ hipError_t multi_dispatch(void* dst, const void* const* srcs, int nsrc, int64_t 
     int64_t grid = (n + kBlock - 1) / kBlock;
     if (grid > kNumCUs * 16) grid = kNumCUs * 16;
     if (grid < 1) grid = 1;
-    hipLaunchKernelGGL((multi_sum_scalar_kernel<DT>), dim3((unsigned)grid), dim3(kBlock), 0, s, dst, sl, nsrc, n);
+    hipLaunchKernelGGL((multi_sum_scalar_kernel<DT, SC...>), dim3((unsigned)grid), dim3(kBlock), 0, s, dst, sl, nsrc, n,
+                       sc...);
     return hipGetLastError();
   }
   // Two sources: the fold is one add, i.e. the 2-input sum, whose launch (one 16-B vector per lane
   // per operand, buffer ops) runs 2 x 128 MiB at the sum's rate instead of the fold's 0.75 of HBM
   // (VERDICT r05 item 6). Storage-type arithmetic for these four types: bit-identical to the fold.
-  if (!remote && nsrc == 2 && (DT == kF32 || DT == kF64 || DT == kI32 || DT == kI64))
-    return sum2_dispatch<DT>(dst, srcs[0], srcs[1], n, kDefMode, kDefUnroll, kDefNT, 0, kDefThreads, s);
+  if (!remote && nsrc == 2 && (DT == kF32 || DT == kF64 || DT == kI32 || DT == kI64)) {
+    if constexpr (sizeof...(SC) == 0) return sum2_dispatch<DT>(dst, srcs[0], srcs[1], n, kDefMode, kDefUnroll, kDefNT, 0, kDefThreads, s);
+    else return sum2_scaled_dispatch<DT>(dst, srcs[0], srcs[1], n, sc..., s);
+  }
   if (remote) {
     switch (nsrc) {
 #define TIPS_REMOTE_CASE(K) \
@@ -1723,22 +1928,22 @@ hipError_t multi_dispatch(void* dst, const void* const* srcs, int nsrc, int64_t 
     }
   }
   switch (nsrc) {
-    case 1: return run_multi<DT, 1>(dst, sl, n, s);
-    case 2: return run_multi<DT, 2>(dst, sl, n, s);
-    case 3: return run_multi<DT, 3>(dst, sl, n, s);
-    case 4: return run_multi<DT, 4>(dst, sl, n, s);
-    case 5: return run_multi<DT, 5>(dst, sl, n, s);
-    case 6: return run_multi<DT, 6>(dst, sl, n, s);
-    case 7: return run_multi<DT, 7>(dst, sl, n, s);
-    case 8: return run_multi<DT, 8>(dst, sl, n, s);
-    case 9: return run_multi<DT, 9>(dst, sl, n, s);
-    case 10: return run_multi<DT, 10>(dst, sl, n, s);
-    case 11: return run_multi<DT, 11>(dst, sl, n, s);
-    case 12: return run_multi<DT, 12>(dst, sl, n, s);
-    case 13: return run_multi<DT, 13>(dst, sl, n, s);
-    case 14: return run_multi<DT, 14>(dst, sl, n, s);
-    case 15: return run_multi<DT, 15>(dst, sl, n, s);
-    case 16: return run_multi<DT, 16>(dst, sl, n, s);
+    case 1: return run_multi<DT, 1>(dst, sl, n, s, sc...);
+    case 2: return run_multi<DT, 2>(dst, sl, n, s, sc...);
+    case 3: return run_multi<DT, 3>(dst, sl, n, s, sc...);
+    case 4: return run_multi<DT, 4>(dst, sl, n, s, sc...);
+    case 5: return run_multi<DT, 5>(dst, sl, n, s, sc...);
+    case 6: return run_multi<DT, 6>(dst, sl, n, s, sc...);
+    case 7: return run_multi<DT, 7>(dst, sl, n, s, sc...);
+    case 8: return run_multi<DT, 8>(dst, sl, n, s, sc...);
+    case 9: return run_multi<DT, 9>(dst, sl, n, s, sc...);
+    case 10: return run_multi<DT, 10>(dst, sl, n, s, sc...);
+    case 11: return run_multi<DT, 11>(dst, sl, n, s, sc...);
+    case 12: return run_multi<DT, 12>(dst, sl, n, s, sc...);
+    case 13: return run_multi<DT, 13>(dst, sl, n, s, sc...);
+    case 14: return run_multi<DT, 14>(dst, sl, n, s, sc...);
+    case 15: return run_multi<DT, 15>(dst, sl, n, s, sc...);
+    case 16: return run_multi<DT, 16>(dst, sl, n, s, sc...);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1771,12 +1976,50 @@ hipError_t launch_multi_sum(void* dst, const void* const* srcs, int nsrc, int64_
     return hipMemcpyAsync(dst, srcs[0], (size_t)n * dtype_size(dtype), hipMemcpyDeviceToDevice, s);
   }
   switch (dtype) {
-    case kF32: return multi_dispatch<kF32>(dst, srcs, nsrc, n, s);
-    case kF64: return multi_dispatch<kF64>(dst, srcs, nsrc, n, s);
-    case kI32: return multi_dispatch<kI32>(dst, srcs, nsrc, n, s);
-    case kI64: return multi_dispatch<kI64>(dst, srcs, nsrc, n, s);
-    case kF16: return multi_dispatch<kF16>(dst, srcs, nsrc, n, s);
-    case kBF16: return multi_dispatch<kBF16>(dst, srcs, nsrc, n, s);
+    case kF32: return multi_dispatch<kF32>(dst, srcs, nsrc, n, s, false);
+    case kF64: return multi_dispatch<kF64>(dst, srcs, nsrc, n, s, false);
+    case kI32: return multi_dispatch<kI32>(dst, srcs, nsrc, n, s, false);
+    case kI64: return multi_dispatch<kI64>(dst, srcs, nsrc, n, s, false);
+    case kF16: return multi_dispatch<kF16>(dst, srcs, nsrc, n, s, false);
+    case kBF16: return multi_dispatch<kBF16>(dst, srcs, nsrc, n, s, false);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+namespace {
+template <int DT>
+ScaleArgs<DT> scale_args(double pre, double post, unsigned raw) {
+  using T = typename WorkOf<DT>::T;
+  return ScaleArgs<DT>{(T)pre, (T)post, raw};  // the factors' one conversion to the working type
+}
+}  // namespace
+
+hipError_t launch_sum2_scaled(void* dst, const void* a, const void* b, int64_t n, int dtype, double pre, double post,
+                              unsigned raw, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  raw &= 3u;
+  if ((pre == 1.0 || raw == 0) && post == 1.0) return launch_sum2(dst, a, b, n, dtype, s);
+  switch (dtype) {
+    case kF32: return sum2_scaled_dispatch<kF32>(dst, a, b, n, scale_args<kF32>(pre, post, raw), s);
+    case kF64: return sum2_scaled_dispatch<kF64>(dst, a, b, n, scale_args<kF64>(pre, post, raw), s);
+    case kF16: return sum2_scaled_dispatch<kF16>(dst, a, b, n, scale_args<kF16>(pre, post, raw), s);
+    case kBF16: return sum2_scaled_dispatch<kBF16>(dst, a, b, n, scale_args<kBF16>(pre, post, raw), s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, double pre,
+                                   double post, unsigned raw, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (nsrc < 1 || nsrc > kMaxSrcs) return hipErrorInvalidValue;
+  raw &= (1u << nsrc) - 1u;
+  if ((pre == 1.0 || raw == 0) && post == 1.0) return launch_multi_sum(dst, srcs, nsrc, n, dtype, s);
+  if (nsrc == 1) return launch_scale_buf(dst, srcs[0], n, dtype, raw ? pre : 1.0, post, s);
+  switch (dtype) {
+    case kF32: return multi_dispatch<kF32>(dst, srcs, nsrc, n, s, false, scale_args<kF32>(pre, post, raw));
+    case kF64: return multi_dispatch<kF64>(dst, srcs, nsrc, n, s, false, scale_args<kF64>(pre, post, raw));
+    case kF16: return multi_dispatch<kF16>(dst, srcs, nsrc, n, s, false, scale_args<kF16>(pre, post, raw));
+    case kBF16: return multi_dispatch<kBF16>(dst, srcs, nsrc, n, s, false, scale_args<kBF16>(pre, post, raw));
     default: return hipErrorInvalidValue;
   }
 }

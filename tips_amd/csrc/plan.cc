@@ -27,13 +27,15 @@ void xfer(PStep& st, int send, int peer, PRef where, int64_t bytes) {
   if (bytes > 0) st.xfers.push_back(PXfer{send, peer, where, bytes});  // empty transfers are skipped on both sides
 }
 
-void sum_of(PStep& st, PRef dst, const PRef* srcs, int nsrc, int64_t count) {
+void sum_of(PStep& st, PRef dst, const PRef* srcs, int nsrc, int64_t count, unsigned raw, int last) {
   if (count <= 0) return;
   PSum s{};
   s.dst = dst;
   s.nsrc = nsrc;
   for (int j = 0; j < nsrc; j++) s.src[j] = srcs[j];
   s.count = count;
+  s.raw = raw;
+  s.last = last;
   st.sums.push_back(s);
 }
 
@@ -59,7 +61,9 @@ void ring(Plan& pl) {
       xfer(st, 1, next, at(s == 0 ? kBufIn : kBufOut, ss.b * es), ss.len() * es);
       xfer(st, 0, prev, land, rs.len() * es);
       const PRef srcs[2] = {at(kBufIn, rs.b * es), land};
-      sum_of(st, at(kBufOut, rs.b * es), srcs, 2, rs.len());
+      // scaled: the local input is always raw; what arrives is raw only at step 0 (later steps
+      // receive a partial sum); the step p-2 sum completes the chunk
+      sum_of(st, at(kBufOut, rs.b * es), srcs, 2, rs.len(), s == 0 ? 3u : 1u, s == p - 2);
       pl.steps.push_back(st);
     }
   }
@@ -100,7 +104,7 @@ void direct(Plan& pl) {
     PRef srcs[tips::kMaxSrcs];
     for (int j = 0; j < p; j++)
       srcs[j] = (j == r) ? at(kBufIn, ms.b * es) : at(kBufStaging, slot(j) + (ms.b - mine.b) * es);
-    sum_of(st, at(kBufOut, ms.b * es), srcs, p, ms.len());
+    sum_of(st, at(kBufOut, ms.b * es), srcs, p, ms.len(), (1u << p) - 1u, 1);  // (scaled: p raw slices, complete)
     pl.steps.push_back(st);
   }
   for (int k = 0; k < K; k++) {
@@ -135,7 +139,7 @@ void oneshot(Plan& pl) {
   }
   PRef srcs[tips::kMaxSrcs];
   for (int j = 0; j < p; j++) srcs[j] = (j == r) ? at(kBufIn, 0) : at(kBufStaging, slot(j));
-  sum_of(st, at(kBufOut, 0), srcs, p, pl.n);
+  sum_of(st, at(kBufOut, 0), srcs, p, pl.n, (1u << p) - 1u, 1);  // (scaled: p raw buckets, complete)
   pl.steps.push_back(st);
 }
 

@@ -42,12 +42,17 @@ struct PXfer {
 };
 
 // dst = ((src[0] + src[1]) + ...) over `count` elements: sum2 for nsrc == 2 (ring step), the
-// rank-order fold (multi_sum) otherwise.
+// rank-order fold (multi_sum) otherwise. For a scaled allreduce (result = post * SUM (pre * x)):
+// bit j of `raw` says src[j] is a rank's input no sum has read yet (multiplied by pre here), and
+// `last` that dst holds every rank's contribution after this sum (multiplied by post here). A
+// plain allreduce ignores both, and tips_schedule_plan does not dump them.
 struct PSum {
   PRef dst;
   int nsrc;
   PRef src[tips::kMaxSrcs];
   int64_t count;
+  unsigned raw;
+  int last;
 };
 
 struct PStep {

@@ -278,8 +278,14 @@ inline bool peer_selected(const State& st) {
 int ensure_comm(State& st);
 void rccl_env_defaults();  // before any ncclCommInitRank of ours
 
-// schedules.cc: device-resident allreduce, caller holds st.mu
-int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype, hipStream_t stream);
+// schedules.cc: device-resident allreduce, caller holds st.mu. With a scale (sc.on(); float dtypes):
+// out = post * SUM over ranks of (pre * in), the factors applied inside the schedule's sum kernels
+// (unfused under TIPS_ALGO_RCCL / TIPS_ALGO_PEER); never captured or replayed as a graph.
+int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype, hipStream_t stream,
+                     const tips::Scale& sc = tips::Scale());
+// the checks every scaled entry point makes on its factors: TIPS_ERR_INVALID_ARG for a non-finite
+// one, TIPS_ERR_UNSUPPORTED for an integer dtype with a factor that is not 1
+int check_scale(int dtype, double pre, double post);
 // the candidates TIPS_ALGO_TUNE times for a bucket of n elements on p ranks, in its order (schedules.cc)
 std::vector<Choice> tune_candidates(int p, int64_t n, int dtype);
 void graphs_release(State& st);  // schedules.cc (shutdown, before the communicator goes)
@@ -298,7 +304,8 @@ void peer_release(State& st);  // collective (shutdown)
 int peer_broadcast(State& st, const char* in, char* out, int64_t bytes, int root, hipStream_t stream);
 int peer_allgatherv(State& st, const char* in, char* out, const int64_t* bytes, const int64_t* displ, hipStream_t stream);
 // host_staging.cc: host-resident allreduce over pipelined pieces, caller holds st.mu
-int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, int dtype);
+int allreduce_host_pipelined(State& st, const char* in, char* out, int64_t n, int dtype,
+                             const tips::Scale& sc = tips::Scale());
 // host_staging.cc: many host tensors in one flat stream of page-locked pieces (pack by host threads,
 // H2D -> allreduce -> D2H per piece, unpack into every out - or, with `flat`, the sums into one host
 // buffer of fused_layout's layout); returns when they are written. Caller holds st.mu.
@@ -316,7 +323,8 @@ struct BatchItem {
 int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStream_t stream);
 // The same into one flat output laid out as the buckets (fused_layout's offsets): pack(b) straight
 // into the flat buffer, allreduce there in place; no slot, no unpack. Caller holds st.mu.
-int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t stream);
+int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t stream,
+                         const tips::Scale& sc = tips::Scale());
 int64_t fused_layout(const int64_t* counts, int n, int dtype, int64_t* offsets);  // flat bytes; pure host
 int fusion_stats(State& st, int64_t* v);  // layouts built, layout hits, tables built, table hits
 int64_t fusion_threshold_bytes();

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "rt.h"
 
@@ -197,6 +198,14 @@ bool is_pinned_host(const void* p, int64_t bytes) {
 
 int check_dtype(int dtype) {
   if (tips::dtype_size(dtype) == 0) return fail(TIPS_ERR_INVALID_ARG, "unsupported dtype %d", dtype);
+  return 0;
+}
+
+int check_scale(int dtype, double pre, double post) {
+  if (!std::isfinite(pre) || !std::isfinite(post))
+    return fail(TIPS_ERR_INVALID_ARG, "scale factors must be finite (prescale %g, postscale %g)", pre, post);
+  if ((pre != 1.0 || post != 1.0) && (dtype == TIPS_INT32 || dtype == TIPS_INT64))
+    return fail(TIPS_ERR_UNSUPPORTED, "scaling is defined for float dtypes only (dtype %d)", dtype);
   return 0;
 }
 

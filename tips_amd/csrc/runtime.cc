@@ -249,14 +249,14 @@ int tips_xfer(void* const* dsts, const void* const* srcs, const int64_t* bytes, 
 }
 #endif  // TIPS_DEV
 
-int tips_allreduce(const void* in, void* out, int64_t count, int dtype, int op, void* stream) {
-  TRY(check_dtype(dtype));
-  if (op != TIPS_OP_SUM) return fail(TIPS_ERR_UNSUPPORTED, "only SUM is implemented (op %d)", op);
-  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+// tips_allreduce and tips_allreduce_scaled (sc.on()): one body, so both take the same route - through
+// a running negotiation as an ALLREDUCE request, the pipelined pieces for large host buffers, the
+// staged path for small ones.
+static int allreduce_entry(const void* in, void* out, int64_t count, int dtype, void* stream, const tips::Scale& sc) {
   int routed_rc;
   const int64_t shape[1] = {count};
   if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 1, 0,
-                       [&] { return tips_allreduce(in, out, count, dtype, op, stream); }, &routed_rc))
+                       [&] { return allreduce_entry(in, out, count, dtype, stream, sc); }, &routed_rc))
     return routed_rc;
   State& st = S();
   std::lock_guard<std::mutex> lk(st.mu);
@@ -267,10 +267,59 @@ int tips_allreduce(const void* in, void* out, int64_t count, int dtype, int op, 
   const size_t bytes = (size_t)count * tips::dtype_size(dtype);
   const bool dout = is_device_ptr(out);
   if (!dout && !is_device_ptr(in) && (int64_t)bytes > env_i64("TIPS_HOST_PIECE_BYTES", kHostPieceBytes))
-    return allreduce_host_pipelined(st, (const char*)in, (char*)out, count, dtype);
+    return allreduce_host_pipelined(st, (const char*)in, (char*)out, count, dtype, sc);
   return run_staged(st, in, bytes, out, bytes, (hipStream_t)stream, [&](const void* i, void* o, hipStream_t s) {
-    return allreduce_device(st, i, o, count, dtype, s);
+    return allreduce_device(st, i, o, count, dtype, s, sc);
   });
+}
+
+int tips_allreduce(const void* in, void* out, int64_t count, int dtype, int op, void* stream) {
+  TRY(check_dtype(dtype));
+  if (op != TIPS_OP_SUM) return fail(TIPS_ERR_UNSUPPORTED, "only SUM is implemented (op %d)", op);
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  return allreduce_entry(in, out, count, dtype, stream, tips::Scale());
+}
+
+int tips_allreduce_scaled(const void* in, void* out, int64_t count, int dtype, double prescale, double postscale,
+                          void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_scale(dtype, prescale, postscale));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  return allreduce_entry(in, out, count, dtype, stream, tips::Scale{prescale, postscale});
+}
+
+int tips_scale(void* dst, const void* src, int64_t count, int dtype, double factor, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_scale(dtype, factor, 1.0));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  if (!dst || !src) return fail(TIPS_ERR_INVALID_ARG, "null pointer");
+  HIP_TRY(tips::launch_scale_buf(dst, src, count, dtype, factor, 1.0, (hipStream_t)stream));
+  return 0;
+}
+
+int tips_bucket_sum_scaled(void* dst, const void* a, const void* b, int64_t count, int dtype, double prescale,
+                           double postscale, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_scale(dtype, prescale, postscale));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  if (!dst || !a || !b) return fail(TIPS_ERR_INVALID_ARG, "null pointer");
+  HIP_TRY(tips::launch_sum2_scaled(dst, a, b, count, dtype, prescale, postscale, 3u, (hipStream_t)stream));
+  return 0;
+}
+
+int tips_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, double prescale,
+                          double postscale, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_scale(dtype, prescale, postscale));
+  if (nsrc < 1 || nsrc > tips::kMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1..%d", tips::kMaxSrcs);
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  if (!dst || !srcs) return fail(TIPS_ERR_INVALID_ARG, "null pointer");
+  HIP_TRY(tips::launch_multi_sum_scaled(dst, srcs, nsrc, count, dtype, prescale, postscale, (1u << nsrc) - 1u,
+                                        (hipStream_t)stream));
+  return 0;
 }
 
 }  // extern "C"

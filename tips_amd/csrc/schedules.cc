@@ -22,16 +22,21 @@ namespace tips {
 namespace rt {
 namespace {
 
-int launch_psum(const PSum& s, char* const* base, int dtype, hipStream_t stream) {
+// A scaled allreduce (sc.on()) multiplies the sum's raw sources by pre and, when the sum completes
+// its elements, the result by post - inside the same launch (kernels.hip, scaled forms).
+int launch_psum(const PSum& s, char* const* base, int dtype, hipStream_t stream, const tips::Scale& sc = tips::Scale()) {
   void* dst = base[s.dst.buf] + s.dst.off;
+  const double post = s.last ? sc.post : 1.0;
   if (s.nsrc == 2) {
-    HIP_TRY(tips::launch_sum2(dst, base[s.src[0].buf] + s.src[0].off, base[s.src[1].buf] + s.src[1].off, s.count,
-                              dtype, stream));
+    const void *a = base[s.src[0].buf] + s.src[0].off, *b = base[s.src[1].buf] + s.src[1].off;
+    if (sc.on()) HIP_TRY(tips::launch_sum2_scaled(dst, a, b, s.count, dtype, sc.pre, post, s.raw, stream));
+    else HIP_TRY(tips::launch_sum2(dst, a, b, s.count, dtype, stream));
     return 0;
   }
   const void* srcs[tips::kMaxSrcs];
   for (int j = 0; j < s.nsrc; j++) srcs[j] = base[s.src[j].buf] + s.src[j].off;
-  HIP_TRY(tips::launch_multi_sum(dst, srcs, s.nsrc, s.count, dtype, stream));
+  if (sc.on()) HIP_TRY(tips::launch_multi_sum_scaled(dst, srcs, s.nsrc, s.count, dtype, sc.pre, post, s.raw, stream));
+  else HIP_TRY(tips::launch_multi_sum(dst, srcs, s.nsrc, s.count, dtype, stream));
   return 0;
 }
 
@@ -140,7 +145,8 @@ bool xfers_conflict(const PStep& a, const PStep& b, char* const* base) {
 // latest earlier step on each other lane whose transfers touch its bytes (the ring's allgather
 // forwards what the previous step received). Every other order comes from wait_sum and the
 // compute stream, as with one lane (tests/plan_util.py hazards(lanes=...) checks both).
-int issue_steps(State& st, const Plan& pl, char* const* base, int L = 1, hipStream_t lane0 = nullptr) {
+int issue_steps(State& st, const Plan& pl, char* const* base, int L = 1, hipStream_t lane0 = nullptr,
+                const tips::Scale& sc = tips::Scale()) {
   const size_t nsteps = pl.steps.size();
   std::vector<std::vector<int>> deps(L > 1 ? nsteps : 0);
   std::vector<char> needed(L > 1 ? nsteps : 0, 0);
@@ -182,7 +188,7 @@ int issue_steps(State& st, const Plan& pl, char* const* base, int L = 1, hipStre
     if (!s.sums.empty()) {
       HIP_TRY(hipEventRecord(st.recv_ev.ev[i], cs));
       HIP_TRY(hipStreamWaitEvent(st.comp_stream, st.recv_ev.ev[i], 0));
-      for (const PSum& ps : s.sums) TRY(launch_psum(ps, base, pl.dtype, st.comp_stream));
+      for (const PSum& ps : s.sums) TRY(launch_psum(ps, base, pl.dtype, st.comp_stream, sc));
       HIP_TRY(hipEventRecord(st.sum_ev.ev[i], st.comp_stream));
     }
   }
@@ -410,7 +416,9 @@ int grow_staging(State& st, int64_t bytes) {
   return 0;
 }
 
-int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t user, int L = 1) {
+// A scaled call (sc.on()) is never captured or replayed: a graph would freeze its factors.
+int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t user, int L = 1,
+             const tips::Scale& sc = tips::Scale()) {
   L = std::max(1, std::min(L, (int)pl.steps.size()));
   const size_t nsteps = pl.steps.size();
   void* const stg_before = st.staging.p;
@@ -422,7 +430,7 @@ int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t u
   TRY(st.recv_ev.ensure(nsteps));
   TRY(st.sum_ev.ensure(nsteps));
   char* base[3] = {(char*)in, out, (char*)st.staging.p};
-  const bool eligible = L == 1 && graph_eligible(st, pl, user);
+  const bool eligible = L == 1 && !sc.on() && graph_eligible(st, pl, user);
   bool key_new = false;
   if (eligible) {
     hipGraphExec_t exec = plan_graph(st, pl, base, false, &key_new);
@@ -433,7 +441,7 @@ int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t u
   TRY(prologue(st, user, L));
   // this call's host wait may just have widened the replay limit (replays_mixed): its key counts as
   // seen, so its next call is captured instead of waiting once more
-  if (L == 1 && !eligible && graph_eligible(st, pl, user)) (void)plan_graph(st, pl, base, true, &key_new);
+  if (L == 1 && !eligible && !sc.on() && graph_eligible(st, pl, user)) (void)plan_graph(st, pl, base, true, &key_new);
   // A bucket that waits for a replay at an address never seen before cannot become a replay by
   // its next call. One shape doing that again and again (a buffer reallocated at a new address every
   // step) would wait on every call, and each wait stalls the host until the device has run the
@@ -446,14 +454,15 @@ int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t u
               (long long)pl.n, fresh_wait_limit());
     st.replays_yield = true;
   }
-  TRY(issue_steps(st, pl, base, L));
+  TRY(issue_steps(st, pl, base, L, nullptr, sc));
   return epilogue(st, user, L);
 }
 
-int plan_allreduce(State& st, const Choice& c, const char* in, char* out, int64_t n, int dtype, hipStream_t user) {
+int plan_allreduce(State& st, const Choice& c, const char* in, char* out, int64_t n, int dtype, hipStream_t user,
+                   const tips::Scale& sc = tips::Scale()) {
   Plan pl;
   TRY(build_schedule_plan(c.algo, st.size, st.rank, n, dtype, c.depth > 0 ? c.depth : plan_depth(st.size, n, dtype), &pl));
-  return run_plan(st, pl, in, out, user, c.lanes);
+  return run_plan(st, pl, in, out, user, c.lanes, sc);
 }
 
 // ---------------------------------------------------------------------------
@@ -465,9 +474,23 @@ int size_class(int64_t bytes) {
   return c;  // ceil(log2(bytes))
 }
 
-int run_choice(State& st, const Choice& c, const char* in, char* out, int64_t n, int dtype, hipStream_t s) {
-  if (c.algo == TIPS_ALGO_PEER) return peer_allreduce(st, in, out, n, dtype, s);
-  return plan_allreduce(st, c, in, out, n, dtype, s);
+// The peer schedule and ncclAllReduce do their own sums: a scaled call wraps them unfused - a scaled
+// copy of in into out (pre), the plain allreduce in place on out, a scale of out (post).
+template <class F>
+int scaled_around(const void* in, void* out, int64_t n, int dtype, hipStream_t s, const tips::Scale& sc, F&& inplace) {
+  HIP_TRY(tips::launch_scale_buf(out, in, n, dtype, sc.pre, 1.0, s));
+  TRY(inplace());
+  HIP_TRY(tips::launch_scale_buf(out, out, n, dtype, 1.0, sc.post, s));
+  return 0;
+}
+
+int run_choice(State& st, const Choice& c, const char* in, char* out, int64_t n, int dtype, hipStream_t s,
+               const tips::Scale& sc = tips::Scale()) {
+  if (c.algo == TIPS_ALGO_PEER) {
+    if (sc.on()) return scaled_around(in, out, n, dtype, s, sc, [&] { return peer_allreduce(st, out, out, n, dtype, s); });
+    return peer_allreduce(st, in, out, n, dtype, s);
+  }
+  return plan_allreduce(st, c, in, out, n, dtype, s, sc);
 }
 
 }  // namespace
@@ -603,22 +626,30 @@ int tune(State& st, const char* in, int64_t n, int dtype, hipStream_t user, Choi
 }  // namespace
 
 // device-resident allreduce, caller holds st.mu
-int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype, hipStream_t stream) {
+int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype, hipStream_t stream, const tips::Scale& sc) {
   if (n == 0) return 0;
   const int64_t es = tips::dtype_size(dtype);
   const int algo = resolve_algo(st.algo, st.size, n * es);
   if (algo == TIPS_ALGO_RCCL) {
     TRY(ensure_comm(st));
+    if (sc.on()) HIP_TRY(tips::launch_scale_buf(out, in, n, dtype, sc.pre, 1.0, stream));  // (unfused, as scaled_around)
     TRY(rccl_enter(st, stream));
-    NCCL_TRY(ncclAllReduce(in, out, (size_t)n, nccl_type(dtype), ncclSum, st.comm, stream));
-    return rccl_leave(st, stream);
-  }
-  if (st.size == 1) {  // MPI_Allreduce on one rank returns the input
-    if (in != out) HIP_TRY(tips::launch_copy_buf(out, in, n * es, stream));
+    NCCL_TRY(ncclAllReduce(sc.on() ? out : in, out, (size_t)n, nccl_type(dtype), ncclSum, st.comm, stream));
+    TRY(rccl_leave(st, stream));
+    if (sc.on()) HIP_TRY(tips::launch_scale_buf(out, out, n, dtype, 1.0, sc.post, stream));
     return 0;
   }
-  if (algo == TIPS_ALGO_PEER && st.size <= tips::kMaxSrcs)
+  if (st.size == 1) {  // MPI_Allreduce on one rank returns the input (scaled: the scaled copy, in place too)
+    if (sc.on()) HIP_TRY(tips::launch_scale_buf(out, in, n, dtype, sc.pre, sc.post, stream));
+    else if (in != out) HIP_TRY(tips::launch_copy_buf(out, in, n * es, stream));
+    return 0;
+  }
+  if (algo == TIPS_ALGO_PEER && st.size <= tips::kMaxSrcs) {
+    if (sc.on())
+      return scaled_around(in, out, n, dtype, stream, sc,
+                           [&] { return peer_allreduce(st, (const char*)out, (char*)out, n, dtype, stream); });
     return peer_allreduce(st, (const char*)in, (char*)out, n, dtype, stream);
+  }
   TRY(ensure_comm(st));  // every other schedule moves its bytes over RCCL (no half-built group on failure)
   if (algo == TIPS_ALGO_TUNE) {
     const auto key = std::make_tuple(st.size, dtype, size_class(n * es));
@@ -630,7 +661,7 @@ int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype,
       it = st.tuned.emplace(key, best).first;
       st.tuned_ms[key] = std::move(timed);
     }
-    return run_choice(st, it->second, (const char*)in, (char*)out, n, dtype, stream);
+    return run_choice(st, it->second, (const char*)in, (char*)out, n, dtype, stream, sc);
   }
   int a = algo;
   if (st.size > tips::kMaxSrcs && (a == TIPS_ALGO_DIRECT || a == TIPS_ALGO_ONESHOT || a == TIPS_ALGO_PEER))
@@ -638,7 +669,7 @@ int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype,
   if (a != TIPS_ALGO_DIRECT && a != TIPS_ALGO_ONESHOT) a = TIPS_ALGO_RING;
   // TIPS_LANES (same on every rank): transfer lanes for the explicitly chosen schedules
   const int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(8, env_i64("TIPS_LANES", 1)));
-  return plan_allreduce(st, Choice{a, 0, lanes}, (const char*)in, (char*)out, n, dtype, stream);
+  return plan_allreduce(st, Choice{a, 0, lanes}, (const char*)in, (char*)out, n, dtype, stream, sc);
 }
 
 void lanes_release(State& st) {

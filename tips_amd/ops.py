@@ -41,8 +41,70 @@ def set_consistency_check(enabled):
     _check = bool(enabled)
 
 
+_op_scaling = os.environ.get("TIPS_OP_SCALING", "0") == "1"
+
+
+def set_op_scaling(enabled):
+    """Whether `op`, `prescale_factor`, `postscale_factor` and `gradient_predivide_factor` reach the
+    reduction (TIPS_OP_SCALING=1 sets the initial value). Off, the default, is the reference's
+    behaviour: they are accepted and the result is the plain SUM. On, allreduce / allreduce_grads /
+    DistributedGradientTape / DistributedOptimizer compute postscale * SUM(prescale * x), op=Average
+    dividing postscale by size(), through the scaled entry points of the library (the factors sit
+    inside its sum kernels). The setting, like the factors, must be the same on every rank."""
+    global _op_scaling
+    _op_scaling = bool(enabled)
+
+
+def op_scaling():
+    return _op_scaling
+
+
 def _shape(t):
     return tuple(int(d) for d in t.shape)
+
+
+def _is_integer(t):
+    return tensors.dtype_code(t) in (_lib.INT32, _lib.INT64)
+
+
+def scale_(tensor, factor):
+    """tensor *= factor in place on the device (tips_scale: one multiply per element in fp32, or
+    f64 for float64, rounded once); a contiguous device tensor of a float dtype."""
+    n = tensors.numel(tensor)
+    if n:
+        _lib.call("tips_scale", tensors.data_ptr(tensor), tensors.data_ptr(tensor), n, tensors.dtype_code(tensor),
+                  float(factor), tensors.stream_of(tensor))
+    return tensor
+
+
+def allreduce_scaled_op(tensor, prescale_factor=1.0, postscale_factor=1.0, name=None):
+    """postscale_factor * SUM over ranks of (prescale_factor * tensor), out of place
+    (tips_allreduce_scaled): every element is multiplied by prescale_factor where a sum kernel first
+    reads it and every finished sum by postscale_factor where it is written, each multiply and add a
+    separate IEEE operation in fp32 (f64 for float64), rounded once per kernel - the bytes moved are
+    those of the plain allreduce. Float dtypes; always scales, whatever set_op_scaling says; the
+    factors must be the same on every rank. Device or host tensors, as allreduce_op.
+
+    With a `name` the request goes through the negotiation as the named SUM does today, and the
+    factors are applied UNFUSED around it: a scaled copy (tips_scale), the named SUM, tips_scale of
+    the result - two more passes over the tensor. Device tensors only on that path."""
+    basics.init()
+    code = tensors.dtype_code(tensor)
+    src = tensors.contiguous(tensor)
+    pre, post = float(prescale_factor), float(postscale_factor)
+    n = tensors.numel(src)
+    if name is not None:
+        if not tensors.is_device(src):
+            raise TypeError("allreduce_scaled with a name takes a device tensor (tips_scale runs on the device)")
+        tmp = tensors.empty_like(src)
+        if n:
+            _lib.call("tips_scale", tensors.data_ptr(tmp), tensors.data_ptr(src), n, code, pre, tensors.stream_of(src))
+        return scale_(synchronize(allreduce_async(tmp, _normalize_name(name))), post)
+    out = _HOST_OUT.take(src) if not tensors.is_device(src) else tensors.empty_like(src)
+    if n:
+        _lib.call("tips_allreduce_scaled", tensors.data_ptr(src), tensors.data_ptr(out), n, code, pre, post,
+                  tensors.stream_of(src))
+    return out
 
 
 def allreduce_op(tensor, name=None):
@@ -239,14 +301,18 @@ def fused_allreduce(tensor_list, out_list=None):
 _WIRE_CODES = {"float16": _lib.FLOAT16, "bfloat16": _lib.BFLOAT16}
 
 
-def fused_allreduce_cast(tensor_list, wire="float16"):
+def fused_allreduce_cast(tensor_list, wire="float16", scale=None):
     """SUM of a list of float32 device tensors reduced in a 16-bit wire type
     (tips_fused_allreduce_cast): each tensor is cast to `wire` (round to nearest even) as it is
     packed into a fusion bucket, every bucket is allreduced in the wire type, and the sums are cast
     back to float32 as they are unpacked - Compression.fp16's compress -> allreduce -> decompress
     (tips/tensorflow/compression.py:49-66) with one pack and one unpack launch per bucket instead of
     two casts per tensor. Returns float32 views of one flat buffer (reused, as fused_allreduce_flat's,
-    once every view is released); inputs unchanged."""
+    once every view is released); inputs unchanged.
+
+    scale = (prescale, postscale): the cast path as above, then ONE tips_scale of the float32 flat
+    output buffer by prescale * postscale - unfused (one more pass over the outputs), and the 16-bit
+    sums on the wire are not predivided."""
     basics.init()
     if not tensor_list:
         return []
@@ -255,7 +321,7 @@ def fused_allreduce_cast(tensor_list, wire="float16"):
         raise TypeError("fused_allreduce_cast: float32 tensors only (got dtype code %d)" % code)
     if wire not in _WIRE_CODES:
         raise ValueError("fused_allreduce_cast: wire must be one of %s" % sorted(_WIRE_CODES))
-    res = _dev_list_cast(tensor_list, _WIRE_CODES[wire])  # (dense, contiguous, one device: C++ reads the list)
+    res = _dev_list_cast(tensor_list, _WIRE_CODES[wire], scale)  # (dense, contiguous, one device: C++ reads the list)
     if res is not None:
         return res
     fo = _flat_outputs(tensor_list, code)
@@ -263,6 +329,8 @@ def fused_allreduce_cast(tensor_list, wire="float16"):
     pi, _keep1 = _lib.ptr_array([t.data_ptr() for t in tensor_list])
     _lib.call("tips_fused_allreduce_cast", pi, _out_ptrs(fo, flat), fo.cp[0], len(tensor_list), code, _WIRE_CODES[wire],
               tensors.stream_of(tensor_list[0]))
+    if scale is not None:
+        scale_(flat, float(scale[0]) * float(scale[1]))
     return views
 
 
@@ -324,17 +392,18 @@ def _layout_settings():
     return (env.get("TIPS_FUSION_THRESHOLD"), env.get("TIPS_COPY_TILE_BYTES"), env.get("TIPS_FUSION_BALANCE"))
 
 
-def fused_allreduce_flat(tensor_list):
+def fused_allreduce_flat(tensor_list, scale=None):
     """Out-of-place SUM of a list of same-dtype device tensors (tips_fused_allreduce_flat): the
     outputs are views of ONE flat buffer laid out as the fusion buckets - each bucket packed straight
     into it and allreduced there in place, no slot and no unpack (2 x the bytes of HBM traffic). The
     flat buffer and views are reused for a later call of the same list signature once the caller has
-    released every output (_FlatOutputs). Inputs unchanged."""
+    released every output (_FlatOutputs). Inputs unchanged. scale = (prescale, postscale): each
+    bucket's allreduce carries the factors inside its sums (tips_fused_allreduce_flat_scaled)."""
     basics.init()
     if not tensor_list:
         return []
     code = _check_fusable(tensor_list, "fused_allreduce_flat")
-    return _flat_call(tensor_list, code, [t.data_ptr() for t in tensor_list])
+    return _flat_call(tensor_list, code, [t.data_ptr() for t in tensor_list], scale)
 
 
 def _flat_outputs(tensor_list, code):
@@ -353,9 +422,9 @@ def _flat_outputs(tensor_list, code):
     return fo
 
 
-def _flat_run(fo, tensor_list, ptrs):
+def _flat_run(fo, tensor_list, ptrs, scale=None):
     """tips_fused_allreduce_flat of `tensor_list` (whose data pointers are `ptrs`) into an output set
-    of `fo`; returns the outputs."""
+    of `fo` (with scale = (prescale, postscale): tips_fused_allreduce_flat_scaled); returns the outputs."""
     last = fo.last  # (one read: another thread may replace it)
     if ptrs == last[0]:
         pp = last[1]
@@ -364,6 +433,10 @@ def _flat_run(fo, tensor_list, ptrs):
         fo.last = (ptrs, pp)
     flat, views = fo.take()
     t0 = tensor_list[0]
+    if scale is not None:
+        _lib.call("tips_fused_allreduce_flat_scaled", pp[0], fo.cp[0], len(ptrs), fo.code, flat.data_ptr(),
+                  float(scale[0]), float(scale[1]), _torch_mod().cuda.current_stream(t0.device).cuda_stream)
+        return views
     _lib.call("tips_fused_allreduce_flat", pp[0], fo.cp[0], len(ptrs), fo.code, flat.data_ptr(),
               _torch_mod().cuda.current_stream(t0.device).cuda_stream)
     return views
@@ -382,7 +455,7 @@ _FAST_FLAT = {}   # (scalar type, device, n, shape hash, layout settings) -> (_F
 _CUR_STREAM = None
 
 
-def _dev_list_flat(tensor_list):
+def _dev_list_flat(tensor_list, scale=None):
     """fused_allreduce_flat of a list of dense, contiguous device tensors of one dtype on one
     device, with the per-tensor host work in C++ (_fast.dev_list: data pointers, counts, a hash of
     the shapes): the outputs, or None when the list is not such a list (the caller's general path
@@ -417,12 +490,16 @@ def _dev_list_flat(tensor_list):
     if _CUR_STREAM is None:
         import torch
         _CUR_STREAM = torch.cuda.current_stream
+    if scale is not None:  # (prescale, postscale): the factors inside each bucket's sums
+        _lib.call("tips_fused_allreduce_flat_scaled", bufs[0], fo.cp[0], n, fo.code, flat.data_ptr(), float(scale[0]),
+                  float(scale[1]), _CUR_STREAM(tensor_list[0].device).cuda_stream)
+        return views
     _lib.call("tips_fused_allreduce_flat", bufs[0], fo.cp[0], n, fo.code, flat.data_ptr(),
               _CUR_STREAM(tensor_list[0].device).cuda_stream)
     return views
 
 
-def _dev_list_cast(tensor_list, wire=_lib.FLOAT16):
+def _dev_list_cast(tensor_list, wire=_lib.FLOAT16, scale=None):
     """fused_allreduce_cast of a list of dense, contiguous float32 device tensors on one device,
     with the per-tensor host work in C++ as _dev_list_flat's (Compression.fp16's fast path in
     allreduce_grads); the float32 outputs, or None when the list is not such a list."""
@@ -457,6 +534,8 @@ def _dev_list_cast(tensor_list, wire=_lib.FLOAT16):
         _CUR_STREAM = torch.cuda.current_stream
     _lib.call("tips_fused_allreduce_cast", bufs[0], _out_ptrs(fo, flat), fo.cp[0], n, _lib.FLOAT32, wire,
               _CUR_STREAM(tensor_list[0].device).cuda_stream)
+    if scale is not None:  # unfused: one tips_scale of the float32 output buffer
+        scale_(flat, float(scale[0]) * float(scale[1]))
     return views
 
 
@@ -476,8 +555,8 @@ def _out_ptrs(fo, flat):
     return hit[1]
 
 
-def _flat_call(tensor_list, code, ptrs):
-    return _flat_run(_flat_outputs(tensor_list, code), tensor_list, ptrs)
+def _flat_call(tensor_list, code, ptrs, scale=None):
+    return _flat_run(_flat_outputs(tensor_list, code), tensor_list, ptrs, scale)
 
 
 def fused_allreduce_host(tensor_list, out_list=None):

@@ -18,21 +18,29 @@ keep the faster (_OverlapChoice). Round 3's default was "during"; rehearsals on
 one shared GPU measured it both faster and slower. =1 / =0 fix
 the choice. The rest go through tips_amd.allreduce_grads.
 
-As in the reference, op / prescale / postscale never reach the reduction
-(__init__.py:82-87, 194-201): the gradients are SUMMED over ranks, op=Average
-included. gradient_predivide_factor is validated as the
-reference validates it (__init__.py:408-411) and otherwise has no effect,
-for the same reason.
+By default, as in the reference, op / prescale / postscale never reach the
+reduction (__init__.py:82-87, 194-201): the gradients are SUMMED over ranks,
+op=Average included, and gradient_predivide_factor is validated
+as the reference validates it (__init__.py:408-411) and otherwise has no
+effect. After tips_amd.set_op_scaling(True) (or with TIPS_OP_SCALING=1)
+op=Average averages: every bucket is reduced with tips_allreduce_scaled,
+prescale = 1 / gradient_predivide_factor and postscale =
+gradient_predivide_factor / size(), the factors inside the sum kernels.
 """
 import warnings
 
 Average = 'Average'
 
 
-def _allreduce_flat_(flat):
-    """In-place SUM of one contiguous device tensor over the ranks (tips_allreduce, in == out)."""
+def _allreduce_flat_(flat, scale=None):
+    """In-place SUM of one contiguous device tensor over the ranks (tips_allreduce, in == out); with
+    scale = (prescale, postscale): postscale * SUM(prescale * flat) (tips_allreduce_scaled)."""
     from . import _lib, basics, tensors
     basics.init()
+    if scale is not None:
+        _lib.call("tips_allreduce_scaled", flat.data_ptr(), flat.data_ptr(), flat.numel(), tensors.dtype_code(flat),
+                  float(scale[0]), float(scale[1]), tensors.stream_of(flat))
+        return
     _lib.call("tips_allreduce", flat.data_ptr(), flat.data_ptr(), flat.numel(), tensors.dtype_code(flat), _lib.OP_SUM,
               tensors.stream_of(flat))
 
@@ -320,9 +328,10 @@ class _DistributedOptimizer(object):
     """Wraps a torch.optim.Optimizer; step() allreduces the gradients first (__init__.py:252-335)."""
 
     def __init__(self, optimizer, compression, sparse_as_dense, op, backward_passes_per_step,
-                 average_aggregated_gradients, groups):
+                 average_aggregated_gradients, groups, gradient_predivide_factor=1.0):
         from . import Compression
         self._optimizer = optimizer
+        self._predivide = float(gradient_predivide_factor)
         self._compression = compression if compression is not None else Compression.none
         self._sparse_as_dense = sparse_as_dense
         self._op = op
@@ -353,6 +362,7 @@ class _DistributedOptimizer(object):
             if ps:
                 mib = float(os.environ.get("TIPS_GRAD_BUCKET_MIB", "25"))
                 self._buckets = _GradBuckets(ps, max(1, int(mib * (1 << 20))), self._passes, self._average_aggregated)
+                self._buckets._issue_fn = self._allreduce_flat
                 self._buckets.active = self._overlap_active
                 self._buckets.final_pass = lambda: (self._calls + 1) % self._passes == 0
         import weakref
@@ -367,6 +377,16 @@ class _DistributedOptimizer(object):
                                for p in {id(p): p for g in optimizer.param_groups for p in g["params"]
                                          if p.requires_grad}.values()]
         weakref.finalize(self, _remove_hooks, list(self._count_handles))
+
+    def _scale(self):
+        """(prescale, postscale) the buckets are reduced with, or None for the plain SUM: under
+        set_op_scaling(True), op=Average is prescale 1/f, postscale f/size() for
+        gradient_predivide_factor f."""
+        from . import _average_scale
+        return _average_scale(self._op, self._predivide)
+
+    def _allreduce_flat(self, flat):
+        _allreduce_flat_(flat, self._scale())
 
     def _overlap_active(self):
         """Hooks issue allreduces only once TiPS runs with more than one rank (never initialise
@@ -481,12 +501,15 @@ class _DistributedOptimizer(object):
                         v = flat[o:o + g.numel()].view_as(g)
                         v.copy_(g)
                         p.grad = v
-                _allreduce_flat_(flat)
+                self._allreduce_flat(flat)
+            elif self._scale() is not None:  # (no scaled form of the in-place fusion: one scaled allreduce each)
+                for p in group:
+                    self._allreduce_flat(p.grad)
             else:
                 fl.allreduce_([p.grad for p in group])
         if rest:
             reduced = allreduce_grads([p.grad for p in rest], compression=self._compression, op=self._op,
-                                      sparse_as_dense=self._sparse_as_dense)
+                                      sparse_as_dense=self._sparse_as_dense, **self._predivide_kw())
             for p, r in zip(rest, reduced):
                 if r is not p.grad:
                     p.grad = r.to(p.grad.dtype) if (not r.is_sparse and r.dtype != p.grad.dtype) else r
@@ -515,6 +538,10 @@ class _DistributedOptimizer(object):
         if self._buckets is not None and self._overlap_ready():
             self._overlap.stepped(self._calls // self._passes - 1)
         return out
+
+    def _predivide_kw(self):
+        # (only when set: allreduce_grads is called as before otherwise)
+        return {"gradient_predivide_factor": self._predivide} if self._predivide != 1.0 else {}
 
     def _step_index(self):
         """The optimizer step the gradients being reduced belong to: calls made so far // passes
@@ -549,9 +576,10 @@ class _DistributedGradientTape(object):
     """gradient() computes the gradients, then sums them over the ranks
     (_DistributedGradientTape.gradient, __init__.py:485-488)."""
 
-    def __init__(self, tape, compression, sparse_as_dense, op):
+    def __init__(self, tape, compression, sparse_as_dense, op, gradient_predivide_factor=1.0):
         from . import Compression
         self._tape = tape
+        self._predivide = float(gradient_predivide_factor)
         self._compression = compression if compression is not None else Compression.none
         self._sparse_as_dense = sparse_as_dense
         self._op = op
@@ -565,8 +593,9 @@ class _DistributedGradientTape(object):
         else:
             import torch
             grads = torch.autograd.grad(target, srcs, grad_outputs=output_gradients, allow_unused=True)
+        kw = {"gradient_predivide_factor": self._predivide} if self._predivide != 1.0 else {}
         reduced = allreduce_grads(list(grads), compression=self._compression, op=self._op,
-                                  sparse_as_dense=self._sparse_as_dense)
+                                  sparse_as_dense=self._sparse_as_dense, **kw)
         return reduced[0] if single else reduced
 
 
@@ -583,11 +612,12 @@ def DistributedGradientTape(gradtape=None,
     object: with gradtape=None, gradient(target, sources, output_gradients) differentiates with
     torch.autograd.grad (allow_unused: a source the target does not depend on gets None, as
     tf.GradientTape returns); any object with that gradient() method can be wrapped instead.
-    As for the optimizer, the gradients are SUMMED over ranks for op=Average too (__init__.py:82-87)."""
+    As for the optimizer, the gradients are SUMMED over ranks for op=Average too (__init__.py:82-87)
+    unless set_op_scaling(True): then op=Average averages, through tips_fused_allreduce_flat_scaled."""
     _validate(op, gradient_predivide_factor, num_groups, groups)
     if gradtape is not None and not callable(getattr(gradtape, 'gradient', None)):
         raise ValueError('gradtape must have a gradient(target, sources, output_gradients) method: %s' % gradtape)
-    return _DistributedGradientTape(gradtape, compression, sparse_as_dense, op)
+    return _DistributedGradientTape(gradtape, compression, sparse_as_dense, op, gradient_predivide_factor)
 
 
 def DistributedOptimizer(optimizer,
@@ -604,7 +634,9 @@ def DistributedOptimizer(optimizer,
                          num_groups=0,
                          groups=None):
     """Same arguments and validation as the reference (__init__.py:337-456); `optimizer` is a
-    torch.optim.Optimizer. name / use_locking / device_* are accepted for signature compatibility."""
+    torch.optim.Optimizer. name / use_locking / device_* are accepted for signature compatibility.
+    Under set_op_scaling(True), op=Average (the default) divides by size() inside the reduction and
+    gradient_predivide_factor f moves 1/f of it before the sums (for 16-bit gradients)."""
     groups = _validate(op, gradient_predivide_factor, num_groups, groups)
     try:
         import torch
@@ -614,4 +646,4 @@ def DistributedOptimizer(optimizer,
     if not ok:
         raise ValueError('Provided optimizer doesn\'t inherit from torch.optim.Optimizer: %s' % optimizer)
     return _DistributedOptimizer(optimizer, compression, sparse_as_dense, op, backward_passes_per_step,
-                                 average_aggregated_gradients, groups)
+                                 average_aggregated_gradients, groups, gradient_predivide_factor)
