@@ -7,7 +7,9 @@ LIB      := tips_amd/lib/libtips_hip.so
 SRCS     := tips_amd/csrc/kernels.hip tips_amd/csrc/runtime.cc tips_amd/csrc/rt_common.cc tips_amd/csrc/plan.cc tips_amd/csrc/schedules.cc \
             tips_amd/csrc/fusion.cc tips_amd/csrc/host_staging.cc tips_amd/csrc/control.cc tips_amd/csrc/negotiate.cc tips_amd/csrc/peer.cc \
             tips_amd/csrc/bootstrap.cc
-HDRS     := tips_amd/csrc/kernels.h tips_amd/csrc/rt.h tips_amd/csrc/net.h tips_amd/csrc/plan.h include/tips_hip.h \
+# the tuning sweeps' kernels: the development and sanitizer libraries only
+DEV_SRCS := tips_amd/csrc/kernels_dev.hip
+HDRS     := tips_amd/csrc/kernels.h tips_amd/csrc/kernels_device.h tips_amd/csrc/kernels_dev.h tips_amd/csrc/rt.h tips_amd/csrc/net.h tips_amd/csrc/plan.h include/tips_hip.h \
             include/tips_hip_dev.h
 DEVLIB   := tools/lib/libtips_hip_dev.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-result -fvisibility=hidden
@@ -47,7 +49,7 @@ $(LIB): $(OBJS)
 	@mkdir -p tips_amd/lib
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,-Bsymbolic -o $@ $(OBJS) -lrccl
 
-DEV_OBJS := $(patsubst tips_amd/csrc/%,build/dev/%.o,$(SRCS))
+DEV_OBJS := $(patsubst tips_amd/csrc/%,build/dev/%.o,$(SRCS) $(DEV_SRCS))
 
 build/dev/%.o: tips_amd/csrc/% $(HDRS)
 	@mkdir -p build/dev
@@ -104,7 +106,7 @@ oracle/build/liboracle.so: oracle/oracle.c oracle/oracle.h
 # ThreadSanitizer build of the same sources (host code only: -fsanitize=thread after -Xarch_host;
 # device code unchanged) and its CPU driver - tests/test_tsan.py (the negotiation with threads and
 # callbacks, the host copy pool); tools/_bin/op_body_tsan runs the op-body test on the GPU box
-TSAN_OBJS := $(patsubst tips_amd/csrc/%,build/tsan/%.o,$(SRCS))
+TSAN_OBJS := $(patsubst tips_amd/csrc/%,build/tsan/%.o,$(SRCS) $(DEV_SRCS))
 TSAN_LIB  := tools/lib/libtips_hip_tsan.so
 CLANG     := /opt/rocm/lib/llvm/bin/clang
 

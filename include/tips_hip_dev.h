@@ -74,7 +74,8 @@ TIPS_API int tips_set_sim_transport(int transport);
  * mode 3 = buffer-op forms (nt = cache-policy pair; blocks = bytes of LDS
  * reserved per workgroup, 0-65536, to cap workgroups per CU), mode 4 = LDS-staged
  * through direct-to-LDS loads (unroll 1/2/4, 256 threads), mode 5 = persistent
- * streaming, 256 x unroll workgroups each walking one contiguous range;
+ * streaming, 256 x unroll workgroups each walking one contiguous range, mode 6 =
+ * other workgroup -> tile maps (unroll = stripe in KiB; kernels_dev.hip);
  * unroll = 16-B vectors per lane in flight;
  * nt: 0 plain, 1 non-temporal loads+stores, 2 nt loads only, 3 nt stores only;
  * threads = workgroup size. Non-default variants exist for f32 only
@@ -87,17 +88,17 @@ TIPS_API int tips_sum_variant(void* dst, const void* a, const void* b, int64_t c
  * nsrc 2, 4 or 8, 16-B aligned pointers. variant 0 = global non-temporal
  * loads, 1 = buffer nt loads 1 vector per lane, 2 = the same with 2 vectors,
  * 3 = buffer plain loads, 4 = buffer nt loads 4 vectors per lane; 8-49 = round 5's sweep of
- * tile order, store policy, lanes, workgroups per CU and grid-stride forms (kernels.hip
+ * tile order, store policy, lanes, workgroups per CU and grid-stride forms (kernels_dev.hip
  * run_multi_x lists them; tools/multi_sum_sweep.py); 36 = round 4's shipped fold; 50 = what
  * tips_multi_sum launches now. Others: TIPS_ERR_HIP. tips_multi_sum uses the default chosen from
  * those sweeps. */
 TIPS_API int tips_multi_sum_variant(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, int variant,
                                     void* stream);
 
-/* Tuning entry for the fusion pack / unpack kernel (tools/copy_sweep.py): `tiles` is a device
+/* Tuning entry for the tile-list copy kernels (rounds 1-2's fusion pack / unpack; tools/copy_sweep.py): `tiles` is a device
  * array of ntiles {const char* src; char* dst; int64_t bytes} records (24 B each), every
- * bytes <= max_tile_bytes. variant 0 = the shipped kernel (one tile per workgroup); 1-8 = the
- * grouped kernel (G tiles per workgroup, cache policies: kernels.hip copy_variant_u),
+ * bytes <= max_tile_bytes. variant 0 = one tile per workgroup; 1-8 = the
+ * grouped kernel (G tiles per workgroup, cache policies: kernels_dev.hip copy_variant_u),
  * max_tile_bytes <= 16384 for those. */
 TIPS_API int tips_copy_tiles_variant(const void* tiles, int ntiles, int variant, int64_t max_tile_bytes, void* stream);
 

@@ -31,7 +31,7 @@ def to_work(a, dtype):
 
 
 def bf16_round(w):
-    """kernels.hip bf16_round_bits on a float32 array (round to nearest even, NaNs kept quiet)."""
+    """kernels_device.h bf16_round_bits on a float32 array (round to nearest even, NaNs kept quiet)."""
     x = np.ascontiguousarray(w, dtype=np.float32).view(np.uint32).astype(np.uint64)
     nan = (x & 0x7fffffff) > 0x7f800000
     r = (x + 0x7fff + ((x >> 16) & 1)) >> 16

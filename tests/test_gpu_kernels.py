@@ -180,3 +180,101 @@ def test_xfer_segments(gpu, nseg, shift):
         assert np.array_equal(d[x:x + k], s[x:x + k])
         mask[x:x + k] = True
     assert np.all(d[~mask] == 0xAB)
+
+
+MULTI_VARIANTS = list(range(0, 37)) + list(range(40, 57))
+
+
+@pytest.mark.parametrize("nsrc", [2, 4, 8])
+def test_every_multi_sum_variant_is_exact(gpu, oracle, nsrc):
+    """The fold's sweep variants (tips_multi_sum_variant, f32): 1025 tiles of 256 vectors, so a
+    partial last tile, a 3-element tail, the ITER and 8-run tile orders, and at 8 sources variant
+    36's 4-vector branch. One add order for all of them: bit-exact against the oracle's fold."""
+    import torch
+    from tips_amd import _lib
+    rng = np.random.default_rng(300 + nsrc)
+    n = (1 << 20) + 5
+    ins = [rand(F32, n, rng) for _ in range(nsrc)]
+    devs = [to_dev(x) for x in ins]
+    exp = to_dev(oracle.fold(ins, code=F32, wide_acc=True)).view(torch.int32)
+    out = torch.empty_like(devs[0])
+    pp, _keep = _lib.ptr_array([d.data_ptr() for d in devs])
+    wrong = []
+    for v in MULTI_VARIANTS:
+        out.fill_(float("nan"))
+        _lib.dev_call("tips_multi_sum_variant", out.data_ptr(), pp, nsrc, n, F32, v, stream())
+        torch.cuda.synchronize()
+        if not torch.equal(out.view(torch.int32), exp):
+            wrong.append(v)
+    assert wrong == []
+
+
+def test_multi_sum_variant_refuses_unknown(gpu):
+    import torch
+    from tips_amd import _lib
+    devs = [torch.zeros(4096, device="cuda") for _ in range(3)]
+    out = torch.empty_like(devs[0])
+    pp, _keep = _lib.ptr_array([d.data_ptr() for d in devs])
+    with pytest.raises(_lib.TipsError):  # no variant 37
+        _lib.dev_call("tips_multi_sum_variant", out.data_ptr(), pp, 2, 4096, F32, 37, stream())
+    with pytest.raises(_lib.TipsError):  # the sweeps instantiate 2, 4 and 8 sources only
+        _lib.dev_call("tips_multi_sum_variant", out.data_ptr(), pp, 3, 4096, F32, 1, stream())
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("max_tile_bytes", [4096, 8192, 16384])
+@pytest.mark.parametrize("variant", range(9))
+def test_copy_tiles_variants(gpu, variant, max_tile_bytes):
+    """The tile-list copy kernels of the sweeps (tips_copy_tiles_variant): 37 tiles (5 workgroups of
+    the 8-tile form, the last one partly empty), empty, sub-vector, ragged and full tiles, each side
+    16-B aligned or shifted by 1 or 4 bytes; every byte copied, nothing written outside the tiles."""
+    import torch
+    from tips_amd import _lib
+    rng = np.random.default_rng(1000 * variant + max_tile_bytes)
+    ntiles = 37
+    sizes = [int(x) for x in rng.choice([0, 1, 15, 16, 17, 4095, 4096, max_tile_bytes], size=ntiles)]
+    sizes[:8] = [0, 1, 15, 16, 17, 4095, 4096, max_tile_bytes]
+    sshift = [int(x) for x in rng.choice([0, 1, 4], size=ntiles)]
+    dshift = [int(x) for x in rng.choice([0, 1, 4], size=ntiles)]
+    base, o = [], 64
+    for k in sizes:
+        base.append(o)
+        o += (k + 15) // 16 * 16 + 64
+    src = torch.from_numpy(rng.integers(0, 256, size=o, dtype=np.uint8)).cuda()
+    dst = torch.full((o,), 0xAB, dtype=torch.uint8, device="cuda")
+    assert src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+    rec = np.array([[src.data_ptr() + b + ss, dst.data_ptr() + b + ds, k]
+                    for b, ss, ds, k in zip(base, sshift, dshift, sizes)], dtype=np.int64)
+    tiles = torch.from_numpy(rec).cuda()  # CopyTile {src, dst, bytes}
+    _lib.dev_call("tips_copy_tiles_variant", tiles.data_ptr(), ntiles, variant, max_tile_bytes, stream())
+    torch.cuda.synchronize()
+    d, s = dst.cpu().numpy(), src.cpu().numpy()
+    mask = np.zeros(len(d), dtype=bool)
+    for b, ss, ds, k in zip(base, sshift, dshift, sizes):
+        assert np.array_equal(d[b + ds:b + ds + k], s[b + ss:b + ss + k])
+        mask[b + ds:b + ds + k] = True
+    assert np.all(d[~mask] == 0xAB)
+
+
+N3, N12 = 786432 + 3, 3145728 + 5  # f32: 3 MiB + 12 B, and 12 MiB + 20 B (just over the fold's 12 MiB bound)
+
+
+@pytest.mark.parametrize("dtype,nsrc,n", [
+    (F32, 5, N3),    # 4 vectors per lane
+    (F32, 3, N12),   # uncapped, striped
+    (F32, 4, N12),   # 128 lanes, 8 workgroups per CU
+    (F32, 6, N12),   # 128 lanes, 5 workgroups per CU
+    (BF16, 2, N12),  # the two-source fold that does not take the sum's launch
+])
+def test_multi_sum_launch_shapes(gpu, oracle, dtype, nsrc, n):
+    """tips_multi_sum at the sizes where the fold changes its launch shape (source count x bytes)."""
+    import torch
+    from tips_amd import _lib
+    rng = np.random.default_rng(400 + nsrc * 7 + dtype)
+    ins = [rand(dtype, n, rng) for _ in range(nsrc)]
+    devs = [to_dev(x) for x in ins]
+    out = torch.empty_like(devs[0])
+    pp, _keep = _lib.ptr_array([d.data_ptr() for d in devs])
+    _lib.call("tips_multi_sum", out.data_ptr(), pp, nsrc, n, dtype, stream())
+    torch.cuda.synchronize()
+    assert same_bits(from_dev(out, dtype), oracle.fold(ins, code=dtype, wide_acc=True), dtype)

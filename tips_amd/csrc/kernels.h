@@ -39,24 +39,6 @@ hipError_t launch_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc,
 // dst = (src * pre) * post over n elements, in place allowed (tips_scale; the scaled allreduce at one rank).
 hipError_t launch_scale_buf(void* dst, const void* src, int64_t n, int dtype, double pre, double post, hipStream_t s);
 
-// Batched byte copy for fusion pack/unpack: one workgroup per tile.
-struct CopyTile {
-  const char* src;
-  char* dst;
-  int64_t bytes;  // <= kCopyTileBytes
-};
-constexpr int64_t kCopyTileBytes = 64 * 1024;
-hipError_t launch_copy_tiles(const CopyTile* tiles_dev, int ntiles, hipStream_t s);
-// The fusion pack / unpack launcher: copy_tiles_g_kernel, one tile of <= 16 KiB per workgroup
-// held in registers (nt loads, sc1 stores, 16-B vectors + bytewise tail): 0-9 % faster than
-// copy_tiles_kernel on the configs' tensor lists (tools/copy_sweep.py); larger tiles fall back.
-hipError_t launch_pack_tiles(const CopyTile* tiles_dev, int ntiles, int64_t max_tile_bytes, hipStream_t s);
-// Tuning sweep (tools/copy_sweep.py): 0 = the shipped kernel; 1-8 = copy_tiles_g_kernel with G
-// tiles per workgroup and load / store cache policies (kernels.hip); tiles of at most
-// max_tile_bytes (<= 16 KiB for variants 1-8).
-hipError_t launch_copy_tiles_variant(const CopyTile* tiles_dev, int ntiles, int variant, int64_t max_tile_bytes,
-                                     hipStream_t s);
-
 // Segment copy over a virtual byte space (fusion pack / unpack / identity copy, fusion.cc): tensor
 // k occupies virtual bytes [begin, end) and byte v of it lives at src + v on the source side and
 // dst + v on the destination side. Tiles of tile_bytes (4, 8 or 16 KiB) are cut from the virtual
@@ -117,19 +99,5 @@ struct XferSeg {
 constexpr int kMaxXferSegs = 16;
 constexpr int64_t kXferTileBytes = 16 * 1024;  // per workgroup: 256 lanes x 4 x 16 B
 hipError_t launch_xfer(const XferSeg* segs, int nseg, hipStream_t s);
-
-// Tuning/sweep entry for the multi-input sum (f32, nsrc 2/4/8); variants in kernels.hip.
-hipError_t launch_multi_sum_variant(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, int variant,
-                                   hipStream_t s);
-
-// Tuning/sweep entry: explicit variant of the 2-input sum.
-//   mode 0 = grid-stride over (blocks) workgroups, mode 1 = one tile per workgroup
-//   unroll = 16-B vectors per lane in flight, nt: 0 plain, 1 non-temporal loads+stores,
-//   2 nt loads only, 3 nt stores only; threads = workgroup size. Non-default variants are f32 only.
-//   mode 3 = buffer-op forms (nt = cache-policy pair index), mode 4 = LDS-staged through gfx950's
-//   direct-to-LDS loads (unroll 1, 2 or 4; 256 threads), mode 5 = persistent streaming (unroll =
-//   workgroups per CU: 1, 2, 4 or 8).
-hipError_t launch_sum2_variant(void* dst, const void* a, const void* b, int64_t n, int dtype, int mode, int unroll,
-                               int nt, int blocks, int threads, hipStream_t s);
 
 }  // namespace tips

@@ -31,8 +31,6 @@
 namespace tips {
 namespace rt {
 
-using tips::CopyTile;
-
 constexpr int64_t kAlignBytes = 256;  // chunk / bucket-slot alignment (dwordx4 + 128-B lines)
 // chunks of at least this many bytes always run pipelined under TIPS_ALGO_TUNE (K >= 2 sub-chunks)
 constexpr int64_t kPipelineMinChunk = (int64_t)16 << 20;

@@ -16,6 +16,9 @@
 #include <string>
 
 #include "rt.h"
+#ifdef TIPS_DEV
+#include "kernels_dev.h"
+#endif
 
 namespace tips {
 int bootstrap_exchange(int rank, int size, const char* host, int port, void* id, int id_bytes, int timeout_s,

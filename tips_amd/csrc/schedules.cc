@@ -23,7 +23,7 @@ namespace rt {
 namespace {
 
 // A scaled allreduce (sc.on()) multiplies the sum's raw sources by pre and, when the sum completes
-// its elements, the result by post - inside the same launch (kernels.hip, scaled forms).
+// its elements, the result by post - inside the same launch (kernels_device.h, scaled forms).
 int launch_psum(const PSum& s, char* const* base, int dtype, hipStream_t stream, const tips::Scale& sc = tips::Scale()) {
   void* dst = base[s.dst.buf] + s.dst.off;
   const double post = s.last ? sc.post : 1.0;

@@ -89,7 +89,7 @@ int main(int argc, char** argv) {
   vs.push_back({"default", -3, 0, 0, 0, 0, {}});
   vs.push_back({"multi_sum_8src", -4, 0, 0, 0, 0, {}});  // 8 x (n/8) sources -> n/8 output (direct-algorithm kernel)
   const char* ntn[] = {"", "_nt", "_ntld", "_ntst"};
-  // (mode 1 = one tile per workgroup) unroll, nt, threads — the f32 variants kernels.hip instantiates
+  // (mode 1 = one tile per workgroup) unroll, nt, threads — the f32 variants kernels_dev.hip instantiates
   const int tiles[][3] = {{1, 0, 256}, {2, 0, 256}, {4, 0, 256}, {8, 0, 256}, {1, 1, 256}, {2, 1, 256}, {4, 1, 256},
                           {8, 1, 256}, {2, 2, 256}, {4, 2, 256}, {2, 3, 256}, {4, 3, 256}, {2, 1, 512}, {4, 1, 512},
                           {8, 1, 512}, {1, 1, 1024}, {2, 1, 1024}, {4, 1, 1024}, {4, 2, 512}, {4, 3, 512},
