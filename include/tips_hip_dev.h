@@ -95,6 +95,11 @@ TIPS_API int tips_sum_variant(void* dst, const void* a, const void* b, int64_t c
 TIPS_API int tips_multi_sum_variant(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, int variant,
                                     void* stream);
 
+/* The peer schedule's pull-fold launch on its own (tests): tips_multi_sum's arguments, checks and
+ * result, through the launch shape peer.cc uses for sources in peer memory (4 vectors per lane,
+ * 256 lanes, for every nsrc 2..16) - otherwise reachable only from multi-process peer jobs. */
+TIPS_API int tips_multi_sum_remote(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, void* stream);
+
 /* Tuning entry for the tile-list copy kernels (rounds 1-2's fusion pack / unpack; tools/copy_sweep.py): `tiles` is a device
  * array of ntiles {const char* src; char* dst; int64_t bytes} records (24 B each), every
  * bytes <= max_tile_bytes. variant 0 = one tile per workgroup; 1-8 = the

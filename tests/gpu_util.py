@@ -21,14 +21,22 @@ def rand(dtype, n, rng, kind="normal"):
 
 
 def with_specials(a, dtype):
+    """a with +-inf, NaN, +-0 in elements 0-4 and, when it has more than 8 elements, the smallest
+    subnormal, the largest finite value and the largest subnormal in elements 6, 7 and 8."""
     a = a.copy()
     if dtype in (F32, F64, F16):
         sp = np.array([np.inf, -np.inf, np.nan, 0.0, -0.0], dtype=NPDT[dtype])
         a[:len(sp)] = sp[:len(a)]
         if len(a) > 8:
-            tiny = np.array([1], dtype={F32: np.uint32, F64: np.uint64, F16: np.uint16}[dtype]).view(NPDT[dtype])[0]
-            a[6] = tiny
+            U, mant = {F32: (np.uint32, 23), F64: (np.uint64, 52), F16: (np.uint16, 10)}[dtype]
+            a[6] = np.array([1], dtype=U).view(NPDT[dtype])[0]
             a[7] = np.finfo(NPDT[dtype]).max
+            a[8] = np.array([(1 << mant) - 1], dtype=U).view(NPDT[dtype])[0]
+    elif dtype == BF16:  # the same values as bit patterns
+        sp = np.array([0x7f80, 0xff80, 0x7fc0, 0x0000, 0x8000], dtype=np.uint16)
+        a[:len(sp)] = sp[:len(a)]
+        if len(a) > 8:
+            a[6], a[7], a[8] = 0x0001, 0x7f7f, 0x007f
     return a
 
 

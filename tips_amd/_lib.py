@@ -180,6 +180,8 @@ _DEV_SIGNATURES = [
       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     ("tips_multi_sum_variant", ctypes.c_int,
      [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    ("tips_multi_sum_remote", ctypes.c_int,
+     [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     ("tips_xfer", ctypes.c_int, [_c_void_pp, _c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p]),
     ("tips_copy_tiles_variant", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),

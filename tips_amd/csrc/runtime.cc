@@ -229,6 +229,17 @@ int tips_multi_sum(void* dst, const void* const* srcs, int nsrc, int64_t count, 
 }
 
 #ifdef TIPS_DEV  // (development surface: libtips_hip_dev.so only, include/tips_hip_dev.h)
+int tips_multi_sum_remote(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, void* stream) {
+  TRY(check_dtype(dtype));
+  if (nsrc < 1 || nsrc > tips::kMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1..%d", tips::kMaxSrcs);
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  HIP_TRY(tips::launch_multi_sum_remote(dst, srcs, nsrc, count, dtype, (hipStream_t)stream));
+  return 0;
+}
+#endif  // TIPS_DEV
+
+#ifdef TIPS_DEV  // (development surface: libtips_hip_dev.so only, include/tips_hip_dev.h)
 int tips_copy_tiles_variant(const void* tiles, int ntiles, int variant, int64_t max_tile_bytes, void* stream) {
   if (ntiles < 0 || (ntiles > 0 && !tiles) || max_tile_bytes < 1 || max_tile_bytes > tips::kCopyTileBytes)
     return fail(TIPS_ERR_INVALID_ARG, "bad copy-tile arguments");
