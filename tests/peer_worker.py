@@ -475,15 +475,29 @@ def shapes_case(c, rank, size, L, _lib, sp):
     return {"case": {"shapes": True}, "rc": 0, "ok": not errs, "error": "; ".join(errs)}
 
 
+# "multibucket": a list of 3.2 MB that, at TIPS_FUSION_THRESHOLD=262144, takes the two-slot pipeline
+# past its second bucket in both layouts: 11 buckets of two 120,000-B tensors as f32 (the copy path),
+# 6 of four 60,000-B tensors in a 2-byte wire type (the cast path), the ragged ones riding along, so
+# pack(b + 2) reuses slot b % 2 many times. One tensor of at least the threshold in either layout (reduced where it lies), one
+# empty one, and two ragged ones (1 and 4099 elements) that leave the views after them 4 B off any
+# 16-B boundary.
+MULTIBUCKET_SIZES = [30000] * 5 + [1] + [30000] * 6 + [140000] + [30000] * 5 + [0, 4099] + [30000] * 6
+MULTIBUCKET_THRESHOLD = 262144
+
+
 def workload_sizes(name):
+    if name == "multibucket":
+        return list(MULTIBUCKET_SIZES)
     sys.path.insert(0, os.path.dirname(HERE))
     import bench
     return bench.fused1000_sizes() if name == "config4" else bench.resnet50_grad_sizes()
 
 
 def fused_case(c, rank, size, L, _lib, sp):
-    """BASELINE config 4 (1000 fp32 grads, 2^U(8,17) elements) or config 5 (the 214 ResNet-50
-    gradients) through the fusion buckets, as the named API would run them every step:
+    """BASELINE config 4 (1000 fp32 grads, 2^U(8,17) elements), config 5 (the 214 ResNet-50
+    gradients) or the small many-bucket list (MULTIBUCKET_SIZES; "min_buckets": the fewest buckets
+    the library's cut must give it, "stagger": inplace_separate's tensors off 16-B boundaries)
+    through the fusion buckets, as the named API would run them every step:
     mode "inplace" (tips_fused_allreduce), "layouts" (the same list, views of one buffer on rank 0
     and separate allocations elsewhere: the layout must not depend on addresses), "oop"
     (tips_fused_allreduce_oop), "grads"
@@ -506,11 +520,24 @@ def fused_case(c, rank, size, L, _lib, sp):
     mine = inputs(rank)
     views = list(torch.split(mine, sizes))
     before = mine.clone()
+    if c.get("min_buckets"):
+        # the case is about the buckets past the second: the library's own cut (tips_fused_pack_bucket
+        # with bucket -1: the bucket count) of this list as f32 and as a 2-byte wire type
+        ptrs, _kp = _lib.ptr_array([v.data_ptr() for v in views])
+        counts, _kc = _lib.i64_array(sizes)
+        for dt in (_lib.FLOAT32, _lib.FLOAT16):
+            nb = _lib.call("tips_fused_pack_bucket", ptrs, counts, len(sizes), dt, -1, None, sp)
+            if nb < c["min_buckets"]:
+                return {"case": {"fused": c["fused"], "mode": mode}, "rc": 0, "ok": False,
+                        "error": "dtype %d: %d buckets, the case needs %d" % (dt, nb, c["min_buckets"])}
     if mode == "inplace":  # views of one flat buffer (packed like any tensors: the layout ignores addresses)
         tips_amd.fused_allreduce_(views)
         got = views
     elif mode == "inplace_separate":  # separately allocated tensors: packed into the buckets
-        got = [v.clone() for v in views]
+        if c.get("stagger"):  # ... tensor i starting 4 * (i % 4) bytes past its allocation's 16-B boundary
+            got = [torch.empty(v.numel() + i % 4, device="cuda")[i % 4:].copy_(v) for i, v in enumerate(views)]
+        else:
+            got = [v.clone() for v in views]
         tips_amd.fused_allreduce_(got)
     elif mode == "layouts":  # rank 0: views of one flat buffer; the others: separate tensors
         got = views if rank == 0 else [v.clone() for v in views]

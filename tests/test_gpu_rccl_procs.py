@@ -113,6 +113,42 @@ def test_fusion_pack_launch_variants_over_rccl(gpu, variant):
     check(run_job(3, cases, timeout=600, **env))
 
 
+MULTIBUCKET_COPY_MODES = ("inplace", "inplace_separate", "oop", "grads")
+MULTIBUCKET_CAST_MODES = ("fp16", "fp16_fresh_outputs", "bf16_wire")
+
+
+def multibucket_cases(modes):
+    from peer_worker import MULTIBUCKET_SIZES
+    assert sum(MULTIBUCKET_SIZES) * 4 < 4 << 20 and 0 in MULTIBUCKET_SIZES and 1 in MULTIBUCKET_SIZES
+    return [{"fused": "multibucket", "seed": seed, "mode": m, "min_buckets": 5, "stagger": True}
+            for seed in (17, 18) for m in modes]
+
+
+@pytest.mark.parametrize("variant", ["per_bucket", "merged_signals", "merged_no_signals"])
+@pytest.mark.parametrize("p", [2, 3])
+def test_fusion_pipeline_past_two_buckets_over_rccl(gpu, p, variant):
+    """The two-slot pipeline beyond its first two buckets, which configs 4 and 5 at the default
+    threshold never reach: peer_worker.MULTIBUCKET_SIZES at TIPS_FUSION_THRESHOLD=262144 is 11 buckets
+    as f32 (the copy path) and 6 in a 16-bit wire type (the cast path), so pack(b + 2) reuses slot
+    b % 2 after unpack(b) while allreduce(b + 1) runs; with a tensor over the threshold, an empty
+    one, ragged ones and (inplace_separate) tensors at 0 / 4 / 8 / 12 B past a 16-B boundary. The
+    worker checks the bucket counts (at least 5) with the library's own cut before each case. In
+    place, out of place, allreduce_grads and the fused casts with per-bucket pack launches; the
+    copy modes again with the first two packs merged (TIPS_PACK_MERGE=1), with signal words and
+    without (TIPS_PACK_SIGNALS=0). Two seeds; bit-exact against the oracle's fold / compressed fold."""
+    from peer_worker import MULTIBUCKET_THRESHOLD
+    env = rccl_env("auto")
+    env.update(TIPS_FUSION_THRESHOLD=str(MULTIBUCKET_THRESHOLD))
+    modes = MULTIBUCKET_COPY_MODES
+    if variant == "per_bucket":
+        modes += MULTIBUCKET_CAST_MODES
+    else:
+        env.update(TIPS_PACK_MERGE="1")
+        if variant == "merged_no_signals":
+            env.update(TIPS_PACK_SIGNALS="0")
+    check(run_job(p, multibucket_cases(modes), **env))
+
+
 @pytest.mark.parametrize("p", [2, 3])
 def test_fusion_buckets_mixed_with_a_replayed_list(gpu, p):
     """Config 4's fusion buckets (two of ~41 MB: eager) alternating with a 2.5 MiB list (one bucket,

@@ -90,6 +90,17 @@ struct Table {  // resolved segment records of one pointer set
 
 }  // namespace
 
+// What a layout depends on besides (dtype, counts), as the environment gives it now: the bucket
+// threshold, the tile of the kernels that walk it (the segment copy's or the fused cast's) and
+// whether the buckets are balanced (TIPS_FUSION_BALANCE)
+struct LayoutParams {
+  int64_t threshold, tile;
+  bool balance;
+};
+LayoutParams layout_params(bool cast = false) {
+  return {fusion_threshold_bytes(), cast ? cast_tile_bytes() : copy_tile_bytes(), env_i64("TIPS_FUSION_BALANCE", 1) != 0};
+}
+
 struct Layout {
   uint64_t key = 0;
   int dtype = 0;
@@ -119,8 +130,12 @@ struct Layout {
 // total / B each instead of greedily to the threshold (a greedy split of config 4 leaves a 15 MiB
 // tail bucket, a launch that small ramps up and drains at 4.3 TB/s). A tensor of at least the
 // threshold gets a region of its own after the buckets and is reduced where it lies.
-void build_layout(Layout* L, const int64_t* counts, int n) {
-  const int64_t es = tips::dtype_size(L->dtype), threshold = L->threshold, tile = L->tile;
+void build_layout(Layout* L, int dtype, const LayoutParams& lp, const int64_t* counts, int n) {
+  L->dtype = dtype;
+  L->threshold = lp.threshold;
+  L->tile = lp.tile;
+  L->balance = lp.balance;
+  const int64_t es = tips::dtype_size(dtype), threshold = lp.threshold, tile = lp.tile;
   L->counts.assign(counts, counts + n);
   L->off.assign(n, -1);
   L->bucket.assign(n, -1);
@@ -255,8 +270,9 @@ int upload(State& st, FusionCache& fc, void* dev, const void* src, size_t bytes)
 
 uint64_t fnv(uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; }
 
-Layout* find_layout(State& st, FusionCache& fc, const int64_t* counts, int n, int dtype, int64_t threshold,
-                    int64_t tile, bool balance) {
+Layout* find_layout(State& st, FusionCache& fc, const int64_t* counts, int n, int dtype, const LayoutParams& lp) {
+  const int64_t threshold = lp.threshold, tile = lp.tile;
+  const bool balance = lp.balance;
   uint64_t h = fnv(fnv(fnv(fnv(1469598103934665603ull, (uint64_t)dtype), (uint64_t)threshold), (uint64_t)tile),
                    (uint64_t)balance);
   h = fnv(h, (uint64_t)n);
@@ -279,11 +295,7 @@ Layout* find_layout(State& st, FusionCache& fc, const int64_t* counts, int n, in
   }
   Layout* L = new Layout();
   L->key = h;
-  L->dtype = dtype;
-  L->threshold = threshold;
-  L->tile = tile;
-  L->balance = balance;
-  build_layout(L, counts, n);
+  build_layout(L, dtype, lp, counts, n);
   L->stamp = ++fc.clock;
   fc.layouts.push_back(L);
   fc.layouts_built++;
@@ -521,9 +533,32 @@ FusionCache& cache(State& st) {
   return *st.fusion_cache;
 }
 
-int copy_tiles(const Layout& L, const Table& t, int table, int tile0, int ntiles, hipStream_t s) {
+// How a fused body opens: at N > 1 the bucket stream waits for the inputs too (tensors reduced where
+// they lie start at once), then the list's layout (*L null: it could not be built).
+int open_layout(State& st, FusionCache& fc, const BatchItem* items, int n, int dtype, const LayoutParams& lp,
+                hipStream_t ws, Layout** L) {
+  if (st.size > 1) {
+    HIP_TRY(hipEventRecord(st.ev_start, ws));
+    HIP_TRY(hipStreamWaitEvent(st.bucket_stream, st.ev_start, 0));
+  }
+  std::vector<int64_t> counts((size_t)n);
+  for (int i = 0; i < n; i++) counts[i] = items[i].count;
+  *L = find_layout(st, fc, counts.data(), n, dtype, lp);
+  return 0;
+}
+
+// Table `table` of a pointer set on the device: [2 records per tile | one per segment] (fill_records)
+struct Records {
+  const CopySeg *tiles, *segs;
+};
+Records records(const Layout& L, const Table& t, int table) {
   const CopySeg* base = t.dev + (size_t)table * (2 * (size_t)L.ntiles + L.seg_tensor.size());
-  HIP_TRY(tips::launch_copy_segs(base, base + 2 * L.ntiles, tile0, ntiles, L.tile, copy_store_policy(), s));
+  return {base, base + 2 * L.ntiles};
+}
+
+int copy_tiles(const Layout& L, const Table& t, int table, int tile0, int ntiles, hipStream_t s) {
+  const Records r = records(L, t, table);
+  HIP_TRY(tips::launch_copy_segs(r.tiles, r.segs, tile0, ntiles, L.tile, copy_store_policy(), s));
   return 0;
 }
 
@@ -578,8 +613,8 @@ int pack_buckets(State& st, const Layout& L, const Table& t, int table, int b0, 
       g.sig_value[k] = st.pack_done_value[k] + 1;
     }
   }
-  const CopySeg* base = t.dev + (size_t)table * (2 * (size_t)L.ntiles + L.seg_tensor.size());
-  HIP_TRY(tips::launch_copy_segs_groups(base, base + 2 * L.ntiles, g, L.tile, copy_store_policy(), s));
+  const Records r = records(L, t, table);
+  HIP_TRY(tips::launch_copy_segs_groups(r.tiles, r.segs, g, L.tile, copy_store_policy(), s));
   if (signal)
     for (int k = 0; k < nb; k++) values[k] = ++st.pack_done_value[k];
   return 0;
@@ -589,6 +624,53 @@ int pack_buckets(State& st, const Layout& L, const Table& t, int table, int b0, 
 int wait_packed(State& st, int k, uint64_t value) {
   HIP_TRY(hipStreamWaitValue64(st.bucket_stream, st.pack_done[k], value, hipStreamWaitValueGte, ~0ull));
   return 0;
+}
+
+// pack(0) and pack(1) as one launch (TIPS_PACK_MERGE): `pack(nb)` launches the first nb buckets'
+// packs on the work stream; `wait(b, launched)` makes the bucket stream wait for bucket b of that
+// launch (its signal word or, without signals, the event recorded behind the whole launch).
+struct MergedPacks {
+  std::function<int(int)> pack;
+  std::function<int(int, hipEvent_t)> wait;
+};
+
+// The two-slot pipeline of the slot paths at N > 1 (bucket b lives in slot b % 2, in `dtype`):
+//   work stream:   pack(0) pack(1) | unpack(0) pack(2) | unpack(1) pack(3) | ... unpack(B-1)
+//   bucket stream: allreduce(b) after pack(b); unpack(b) after allreduce(b); pack(b+2) reuses slot
+//                  b % 2 after unpack(b)
+// and the work stream joined behind the bucket stream (so behind whatever the caller queued there
+// for the tensors reduced outside the buckets, too). pack / unpack launch on the work stream.
+template <typename Pack, typename Unpack>
+int slot_pipeline(State& st, const Layout& L, hipStream_t ws, int dtype, Pack pack, Unpack unpack,
+                  const MergedPacks* merged = nullptr, const tips::Scale& sc = tips::Scale()) {
+  const int B = (int)L.buckets.size(), first = std::min(B, 2);
+  const int64_t es = tips::dtype_size(dtype);
+  TRY(st.fuse_ev.ensure(2 * (size_t)B));
+  hipEvent_t* packed = st.fuse_ev.ev.data();
+  hipEvent_t* reduced = st.fuse_ev.ev.data() + B;
+  if (merged) {
+    TRY(merged->pack(first));
+    HIP_TRY(hipEventRecord(packed[0], ws));  // (read without signals: the launch as a whole)
+  } else {
+    for (int b = 0; b < first; b++) {
+      TRY(pack(b));
+      HIP_TRY(hipEventRecord(packed[b], ws));
+    }
+  }
+  for (int b = 0; b < B; b++) {
+    char* slot = (char*)st.fusion.p + (int64_t)(b % 2) * L.threshold;
+    if (merged && b < first) TRY(merged->wait(b, packed[0]));
+    else HIP_TRY(hipStreamWaitEvent(st.bucket_stream, packed[b], 0));
+    TRY(allreduce_device(st, slot, slot, L.buckets[b].bytes / es, dtype, st.bucket_stream, sc));
+    HIP_TRY(hipEventRecord(reduced[b], st.bucket_stream));
+    HIP_TRY(hipStreamWaitEvent(ws, reduced[b], 0));
+    TRY(unpack(b));
+    if (b + 2 < B) {
+      TRY(pack(b + 2));
+      HIP_TRY(hipEventRecord(packed[b + 2], ws));
+    }
+  }
+  return join(ws, st.bucket_stream, st.ev_comp_done);
 }
 
 // A fused call's entry: the work stream (the caller's, or fuse_stream under
@@ -709,11 +791,7 @@ int fusion_stats(State& st, int64_t* v) {
 // The layout's byte offsets, for callers that allocate the flat output (tips_fused_layout).
 int64_t fused_layout(const int64_t* counts, int n, int dtype, int64_t* offsets) {
   Layout L;
-  L.dtype = dtype;
-  L.threshold = fusion_threshold_bytes();
-  L.tile = copy_tile_bytes();
-  L.balance = env_i64("TIPS_FUSION_BALANCE", 1) != 0;
-  build_layout(&L, counts, n);
+  build_layout(&L, dtype, layout_params(), counts, n);
   if (offsets)
     for (int i = 0; i < n; i++) offsets[i] = L.off[i] < 0 ? 0 : L.off[i];
   return L.flat_bytes;
@@ -722,8 +800,8 @@ int64_t fused_layout(const int64_t* counts, int n, int dtype, int64_t* offsets) 
 int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStream_t user) {
   if (n <= 0) return 0;
   FusionCache& fc = cache(st);
-  const int64_t threshold = fusion_threshold_bytes();
-  TRY(ensure_slots(st, fc, threshold));
+  const LayoutParams lp = layout_params();
+  TRY(ensure_slots(st, fc, lp.threshold));
   // One rank: the allreduce of anything is the identity (as allreduce_device's), so a list reduced
   // in place needs no work and one out of place one copy launch - no bucket. TIPS_FUSION_MEASURE_PACK=1
   // keeps the buckets anyway, to measure on one GPU what packing costs a step at N > 1.
@@ -731,18 +809,11 @@ int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStre
   bool in_place = true;
   for (int i = 0; i < n && in_place; i++) in_place = items[i].in == items[i].out || items[i].count == 0;
   if (identity && in_place) return 0;
-  std::vector<int64_t> counts((size_t)n);
-  for (int i = 0; i < n; i++) counts[i] = items[i].count;
   return in_fusion(st, user, [&](hipStream_t ws) -> int {
-    if (st.size > 1) {  // inputs ready for the bucket stream too (the direct tensors start at once)
-      HIP_TRY(hipEventRecord(st.ev_start, ws));
-      HIP_TRY(hipStreamWaitEvent(st.bucket_stream, st.ev_start, 0));
-    }
-    Layout* L = find_layout(st, fc, counts.data(), n, dtype, threshold, copy_tile_bytes(),
-                            env_i64("TIPS_FUSION_BALANCE", 1) != 0);
+    Layout* L = nullptr;
+    TRY(open_layout(st, fc, items, n, dtype, lp, ws, &L));
     if (!L) return TIPS_ERR_HIP;
     if (L->seg_tensor.empty()) return 0;
-    const int64_t es = tips::dtype_size(dtype);
     if (identity) {  // one rank, out of place: every tensor copied in -> out, one launch over the whole space
       Table* t = find_table(st, fc, *L, kCopy, items, n, nullptr);
       if (!t) return TIPS_ERR_HIP;
@@ -753,7 +824,6 @@ int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStre
     if (B && !t) return TIPS_ERR_HIP;
     auto pack = [&](int b) { return copy_tiles(*L, *t, 0, L->buckets[b].tile0, L->buckets[b].ntiles, ws); };
     auto unpack = [&](int b) { return copy_tiles(*L, *t, 1, L->buckets[b].tile0, L->buckets[b].ntiles, ws); };
-    auto slot = [&](int b) { return (char*)st.fusion.p + (int64_t)(b % 2) * threshold; };
     // pack(0) and pack(1) (both slots) go first: one launch when merged, bucket 0's tiles first
     const int first = std::min(B, 2);
     const bool merge = first > 1 && pack_merge(st);
@@ -769,39 +839,23 @@ int fused_allreduce(State& st, const BatchItem* items, int n, int dtype, hipStre
       return 0;
     }
     // bucket stream: the direct tensors first (nothing to pack: their exchange starts at once and
-    //                overlaps pack(0)), then allreduce(b) after pack(b)
-    // work stream:   pack(0) pack(1) | unpack(0) pack(2) | unpack(1) pack(3) | ... unpack(B-1);
-    //                unpack(b) after allreduce(b); pack(b+2) reuses slot b % 2 after unpack(b)
+    // overlaps pack(0)), then the buckets' allreduces
     for (int i : L->direct) TRY(allreduce_device(st, items[i].in, items[i].out, items[i].count, dtype, st.bucket_stream));
-    TRY(st.fuse_ev.ensure(2 * (size_t)B));
-    hipEvent_t* packed = st.fuse_ev.ev.data();
-    hipEvent_t* reduced = st.fuse_ev.ev.data() + B;
+    if (!merge) return slot_pipeline(st, *L, ws, dtype, pack, unpack);
     // merged: the bucket stream waits for each bucket's signal word (or, without signals, for the
     // whole launch)
-    const bool signal = merge && pack_signals_ready(st, ws);
+    bool signal = false;
     uint64_t sigv[2] = {};
-    if (merge) {
-      TRY(pack_buckets(st, *L, *t, 0, 0, first, signal, sigv, ws));
-      HIP_TRY(hipEventRecord(packed[0], ws));  // (read when !signal: the launch as a whole)
-    } else {
-      for (int b = 0; b < first; b++) {
-        TRY(pack(b));
-        HIP_TRY(hipEventRecord(packed[b], ws));
-      }
-    }
-    for (int b = 0; b < B; b++) {
-      if (signal && b < first) TRY(wait_packed(st, b, sigv[b]));
-      else HIP_TRY(hipStreamWaitEvent(st.bucket_stream, packed[merge && b < first ? 0 : b], 0));
-      TRY(allreduce_device(st, slot(b), slot(b), L->buckets[b].bytes / es, dtype, st.bucket_stream));
-      HIP_TRY(hipEventRecord(reduced[b], st.bucket_stream));
-      HIP_TRY(hipStreamWaitEvent(ws, reduced[b], 0));
-      TRY(unpack(b));
-      if (b + 2 < B) {
-        TRY(pack(b + 2));
-        HIP_TRY(hipEventRecord(packed[b + 2], ws));
-      }
-    }
-    return join(ws, st.bucket_stream, st.ev_comp_done);  // (the direct tensors' allreduces too)
+    const MergedPacks merged{[&](int nb) -> int {
+                               signal = pack_signals_ready(st, ws);
+                               return pack_buckets(st, *L, *t, 0, 0, nb, signal, sigv, ws);
+                             },
+                             [&](int b, hipEvent_t launched) -> int {
+                               if (signal) return wait_packed(st, b, sigv[b]);
+                               HIP_TRY(hipStreamWaitEvent(st.bucket_stream, launched, 0));
+                               return 0;
+                             }};
+    return slot_pipeline(st, *L, ws, dtype, pack, unpack, &merged);
   });
 }
 
@@ -814,16 +868,9 @@ int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, vo
                          const tips::Scale& sc) {
   if (n <= 0) return 0;
   FusionCache& fc = cache(st);
-  const int64_t threshold = fusion_threshold_bytes();
-  std::vector<int64_t> counts((size_t)n);
-  for (int i = 0; i < n; i++) counts[i] = items[i].count;
   return in_fusion(st, user, [&](hipStream_t ws) -> int {
-    if (st.size > 1) {
-      HIP_TRY(hipEventRecord(st.ev_start, ws));
-      HIP_TRY(hipStreamWaitEvent(st.bucket_stream, st.ev_start, 0));
-    }
-    Layout* L = find_layout(st, fc, counts.data(), n, dtype, threshold, copy_tile_bytes(),
-                            env_i64("TIPS_FUSION_BALANCE", 1) != 0);
+    Layout* L = nullptr;
+    TRY(open_layout(st, fc, items, n, dtype, layout_params(), ws, &L));
     if (!L) return TIPS_ERR_HIP;
     if (L->seg_tensor.empty()) return 0;
     Table* t = find_table(st, fc, *L, kFlat, items, n, flat);
@@ -870,32 +917,23 @@ int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, vo
 int fused_allreduce_cast(State& st, const BatchItem* items, int n, int wire, hipStream_t user) {
   if (n <= 0) return 0;
   FusionCache& fc = cache(st);
-  const int64_t threshold = fusion_threshold_bytes();
-  TRY(ensure_slots(st, fc, threshold));
-  std::vector<int64_t> counts((size_t)n);
-  for (int i = 0; i < n; i++) counts[i] = items[i].count;
+  const LayoutParams lp = layout_params(/*cast=*/true);
+  TRY(ensure_slots(st, fc, lp.threshold));
   return in_fusion(st, user, [&](hipStream_t ws) -> int {
-    if (st.size > 1) {  // inputs ready for the bucket stream too (the large tensors start at once)
-      HIP_TRY(hipEventRecord(st.ev_start, ws));
-      HIP_TRY(hipStreamWaitEvent(st.bucket_stream, st.ev_start, 0));
-    }
     // the layout of the WIRE type's bytes: buckets of at most the threshold in wire bytes
-    Layout* L = find_layout(st, fc, counts.data(), n, wire, threshold, cast_tile_bytes(),
-                            env_i64("TIPS_FUSION_BALANCE", 1) != 0);
+    Layout* L = nullptr;
+    TRY(open_layout(st, fc, items, n, wire, lp, ws, &L));
     if (!L) return TIPS_ERR_HIP;
     if (L->seg_tensor.empty()) return 0;
     const int64_t es = tips::dtype_size(wire);
     const int B = (int)L->buckets.size();
     Table* t = B ? find_table(st, fc, *L, kSlotCast, items, n, st.fusion.p) : nullptr;
     if (B && !t) return TIPS_ERR_HIP;
-    const size_t per = 2 * (size_t)L->ntiles + L->seg_tensor.size();
-    auto cast = [&](int dir, int b) -> int {
-      const CopySeg* base = t->dev + (size_t)dir * per;
-      HIP_TRY(tips::launch_cast_segs(base, base + 2 * L->ntiles, L->buckets[b].tile0, L->buckets[b].ntiles, L->tile, dir,
-                                     wire, ws));
+    auto cast = [&](int dir, int b) -> int {  // dir 0: f32 -> the slot (pack), 1: back (unpack)
+      const Records r = records(*L, *t, dir);
+      HIP_TRY(tips::launch_cast_segs(r.tiles, r.segs, L->buckets[b].tile0, L->buckets[b].ntiles, L->tile, dir, wire, ws));
       return 0;
     };
-    auto slot = [&](int b) { return (char*)st.fusion.p + (int64_t)(b % 2) * threshold; };
     // tensors of at least the threshold (in wire bytes): one at a time through a scratch buffer of
     // the wire type - cast in, allreduce in place, cast out - on the bucket stream (their exchange
     // starts at once) or, at one rank, on the work stream (the round trip)
@@ -913,28 +951,35 @@ int fused_allreduce_cast(State& st, const BatchItem* items, int n, int wire, hip
       }
       return 0;
     }
-    // as fused_allreduce: pack(0) pack(1) | unpack(0) pack(2) | ..., allreduce(b) on the bucket
-    // stream between pack(b) and unpack(b), in the wire type
-    TRY(st.fuse_ev.ensure(2 * (size_t)B));
-    hipEvent_t* packed = st.fuse_ev.ev.data();
-    hipEvent_t* reduced = st.fuse_ev.ev.data() + B;
-    for (int b = 0; b < std::min(B, 2); b++) {
-      TRY(cast(0, b));
-      HIP_TRY(hipEventRecord(packed[b], ws));
-    }
-    for (int b = 0; b < B; b++) {
-      HIP_TRY(hipStreamWaitEvent(st.bucket_stream, packed[b], 0));
-      TRY(allreduce_device(st, slot(b), slot(b), L->buckets[b].bytes / es, wire, st.bucket_stream));
-      HIP_TRY(hipEventRecord(reduced[b], st.bucket_stream));
-      HIP_TRY(hipStreamWaitEvent(ws, reduced[b], 0));
-      TRY(cast(1, b));
-      if (b + 2 < B) {
-        TRY(cast(0, b + 2));
-        HIP_TRY(hipEventRecord(packed[b + 2], ws));
-      }
-    }
-    return join(ws, st.bucket_stream, st.ev_comp_done);  // (the large tensors' work too)
+    // the buckets in the wire type, packed and unpacked by the cast launches
+    return slot_pipeline(st, *L, ws, wire, [&](int b) { return cast(0, b); }, [&](int b) { return cast(1, b); });
   });
+}
+
+int list_collective(const void* const* ins, const int64_t* counts, int n, int dtype, int announce, ListOuts kind,
+                    void* const* outs, void* flat, bool route, const ListBody& body) {
+  TRY(check_dtype(dtype));
+  if (n < 0 || (n > 0 && (!ins || !counts || (kind == kOutsEach && !outs) || (kind == kOutsFlat && !flat))))
+    return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
+  std::vector<BatchItem> items((size_t)n);
+  int64_t shape[2] = {n, 0};  // what a routed list is announced with: [n, elements]
+  for (int i = 0; i < n; i++) {
+    void* o = kind == kOutsEach ? outs[i] : kind == kOutsFlat ? flat : const_cast<void*>(ins[i]);
+    if (counts[i] < 0 || (counts[i] > 0 && (!ins[i] || !o))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor %d", i);
+    items[i] = BatchItem{ins[i], o, counts[i]};
+    shape[1] += counts[i];
+  }
+  auto locked = [&]() -> int {
+    State& st = S();
+    std::lock_guard<std::mutex> lk(st.mu);
+    if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
+    if (n == 0) return 0;
+    TRY(set_device(st));
+    return body(st, items);
+  };
+  int routed_rc;
+  if (route && route_collective(TIPS_REQ_ALLREDUCE, announce, shape, 2, 0, locked, &routed_rc)) return routed_rc;
+  return locked();
 }
 
 }  // namespace rt
@@ -944,42 +989,12 @@ using namespace tips::rt;
 
 namespace {
 
-int check_list(const void* const* ins, const int64_t* counts, int n, int dtype, std::vector<BatchItem>* items,
-               void* const* outs) {
-  TRY(check_dtype(dtype));
-  if (n < 0 || (n > 0 && (!ins || !counts))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  items->resize((size_t)n);
-  for (int i = 0; i < n; i++) {
-    void* o = outs ? outs[i] : const_cast<void*>(ins[i]);
-    if (counts[i] < 0 || (counts[i] > 0 && (!ins[i] || !o))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor %d", i);
-    (*items)[i] = BatchItem{ins[i], o, counts[i]};
-  }
-  return 0;
-}
-
-// the shape a fused list is announced with when it is routed through the negotiation: [n, elements]
-void list_shape(const int64_t* counts, int n, int64_t* shape) {
-  shape[0] = n;
-  shape[1] = 0;
-  for (int i = 0; i < n; i++) shape[1] += counts[i];
-}
-
 int fused_entry(const void* const* ins, void* const* outs, const int64_t* counts, int n, int dtype, void* stream) {
   if (!outs && n > 0) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  std::vector<BatchItem> items;
-  TRY(check_list(ins, counts, n, dtype, &items, outs));
-  int routed_rc;
-  int64_t shape[2];
-  list_shape(counts, n, shape);
-  if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 2, 0,
-                       [&] { return fused_entry(ins, outs, counts, n, dtype, stream); }, &routed_rc))
-    return routed_rc;
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  TRY(set_device(st));
-  return fused_allreduce(st, items.data(), n, dtype, (hipStream_t)stream);
+  return list_collective(ins, counts, n, dtype, dtype, kOutsEach, outs, nullptr, true,
+                         [&](State& st, std::vector<BatchItem>& items) {
+                           return fused_allreduce(st, items.data(), n, dtype, (hipStream_t)stream);
+                         });
 }
 
 }  // namespace
@@ -1003,22 +1018,11 @@ int tips_fused_allreduce_cast(const void* const* ins, void* const* outs, const i
     return fail(TIPS_ERR_UNSUPPORTED, "tips_fused_allreduce_cast: the wire type must be TIPS_FLOAT16 or TIPS_BFLOAT16 "
                                       "(got %d)", wire_dtype);
   if (!outs && n > 0) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  std::vector<BatchItem> items;
-  TRY(check_list(ins, counts, n, dtype, &items, outs));
-  int routed_rc;
-  int64_t shape[2];
-  list_shape(counts, n, shape);
   // (announced with the wire type: a rank compressing to f16 and one to bf16 fail as mismatched dtypes)
-  if (route_collective(TIPS_REQ_ALLREDUCE, wire_dtype, shape, 2, 0,
-                       [&] { return tips_fused_allreduce_cast(ins, outs, counts, n, dtype, wire_dtype, stream); },
-                       &routed_rc))
-    return routed_rc;
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  TRY(set_device(st));
-  return fused_allreduce_cast(st, items.data(), n, wire_dtype, (hipStream_t)stream);
+  return list_collective(ins, counts, n, dtype, wire_dtype, kOutsEach, outs, nullptr, true,
+                         [&](State& st, std::vector<BatchItem>& items) {
+                           return fused_allreduce_cast(st, items.data(), n, wire_dtype, (hipStream_t)stream);
+                         });
 }
 
 #ifdef TIPS_DEV  // (development surface: libtips_hip_dev.so only, include/tips_hip_dev.h)
@@ -1029,11 +1033,7 @@ int64_t tips_fusion_tile_table(const int64_t* counts, int n, int dtype, const in
   for (int i = 0; i < n; i++)
     if (counts[i] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count %d", i);
   Layout L;
-  L.dtype = dtype;
-  L.threshold = fusion_threshold_bytes();
-  L.tile = copy_tile_bytes();
-  L.balance = env_i64("TIPS_FUSION_BALANCE", 1) != 0;
-  build_layout(&L, counts, n);
+  build_layout(&L, dtype, layout_params(), counts, n);
   std::vector<BatchItem> items((size_t)n);
   for (int i = 0; i < n; i++) items[i] = BatchItem{(const void*)(uintptr_t)ins[i], (void*)(uintptr_t)outs[i], counts[i]};
   std::vector<tips::CopySeg> rec;
@@ -1058,23 +1058,14 @@ int64_t tips_fused_layout(const int64_t* counts, int n, int dtype, int64_t* offs
 
 static int fused_flat_entry(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat, void* stream,
                             const tips::Scale& sc) {
-  std::vector<BatchItem> items;
-  TRY(check_list(ins, counts, n, dtype, &items, nullptr));
-  int routed_rc;
-  int64_t shape[2];
-  list_shape(counts, n, shape);
-  if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 2, 0,
-                       [&] { return fused_flat_entry(ins, counts, n, dtype, flat, stream, sc); }, &routed_rc))
-    return routed_rc;
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  if (!flat) return fail(TIPS_ERR_INVALID_ARG, "null flat output");
-  TRY(set_device(st));
-  if (!is_device_ptr(flat)) return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_flat needs device memory");
-  for (auto& it : items) it.out = it.count ? flat : nullptr;
-  return fused_allreduce_flat(st, items.data(), n, dtype, flat, (hipStream_t)stream, sc);
+  return list_collective(ins, counts, n, dtype, dtype, kOutsNone, nullptr, nullptr, true,
+                         [&](State& st, std::vector<BatchItem>& items) -> int {
+                           if (!flat) return fail(TIPS_ERR_INVALID_ARG, "null flat output");
+                           if (!is_device_ptr(flat))
+                             return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_flat needs device memory");
+                           for (auto& it : items) it.out = it.count ? flat : nullptr;
+                           return fused_allreduce_flat(st, items.data(), n, dtype, flat, (hipStream_t)stream, sc);
+                         });
 }
 
 int tips_fused_allreduce_flat(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat,
@@ -1091,33 +1082,33 @@ int tips_fused_allreduce_flat_scaled(const void* const* ins, const int64_t* coun
 
 int64_t tips_fused_pack_bucket(const void* const* ins, const int64_t* counts, int n, int dtype, int bucket, void* dst,
                                void* stream) {
-  std::vector<BatchItem> items;
-  TRY(check_list(ins, counts, n, dtype, &items, nullptr));
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  TRY(set_device(st));
-  FusionCache& fc = cache(st);
-  Layout* L = find_layout(st, fc, counts, n, dtype, fusion_threshold_bytes(), copy_tile_bytes(),
-                          env_i64("TIPS_FUSION_BALANCE", 1) != 0);
-  if (!L) return TIPS_ERR_HIP;
-  const int B = (int)L->buckets.size();
-  if (bucket < 0) return B;
-  if (bucket >= B || !dst) return fail(TIPS_ERR_INVALID_ARG, "bucket %d of %d", bucket, B);
-  const Bucket& bk = L->buckets[bucket];
-  for (auto& it : items) it.out = (char*)dst - bk.off;
-  // in the fusion chain like any fused call (the table's upload and later reuse stay ordered), with
-  // the chain's event left to the next call that needs it: no marker between back-to-back launches
-  TRY(in_fusion(st, (hipStream_t)stream, [&](hipStream_t ws) -> int {
-    Table* t = find_table(st, fc, *L, kFlat, items.data(), n, (char*)dst - bk.off);
-    if (!t) return TIPS_ERR_HIP;
-    return copy_tiles(*L, *t, 0, bk.tile0, bk.ntiles, ws);
-  }, /*lazy=*/true));
-  int64_t payload = 0;
-  for (int i = 0; i < n; i++)
-    if (L->bucket[i] == bucket) payload += counts[i] * tips::dtype_size(dtype);
-  return payload;
+  int64_t result = 0;  // the bucket count (bucket < 0) or the bucket's payload bytes
+  const int rc = list_collective(
+      ins, counts, n, dtype, dtype, kOutsNone, nullptr, nullptr, /*route=*/false,
+      [&](State& st, std::vector<BatchItem>& items) -> int {
+        FusionCache& fc = cache(st);
+        Layout* L = find_layout(st, fc, counts, n, dtype, layout_params());
+        if (!L) return TIPS_ERR_HIP;
+        const int B = (int)L->buckets.size();
+        if (bucket < 0) {
+          result = B;
+          return 0;
+        }
+        if (bucket >= B || !dst) return fail(TIPS_ERR_INVALID_ARG, "bucket %d of %d", bucket, B);
+        const Bucket& bk = L->buckets[bucket];
+        for (auto& it : items) it.out = (char*)dst - bk.off;
+        // in the fusion chain like any fused call (the table's upload and later reuse stay ordered), with
+        // the chain's event left to the next call that needs it: no marker between back-to-back launches
+        TRY(in_fusion(st, (hipStream_t)stream, [&](hipStream_t ws) -> int {
+          Table* t = find_table(st, fc, *L, kFlat, items.data(), n, (char*)dst - bk.off);
+          if (!t) return TIPS_ERR_HIP;
+          return copy_tiles(*L, *t, 0, bk.tile0, bk.ntiles, ws);
+        }, /*lazy=*/true));
+        for (int i = 0; i < n; i++)
+          if (L->bucket[i] == bucket) result += counts[i] * tips::dtype_size(dtype);
+        return 0;
+      });
+  return rc ? rc : result;
 }
 
 int tips_fusion_stats(int64_t* layouts_built, int64_t* layout_hits, int64_t* tables_built, int64_t* table_hits) {

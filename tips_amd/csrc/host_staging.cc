@@ -645,54 +645,24 @@ int tips_host_pool_selftest(int nthreads, int runs, int njobs) {
 #endif  // TIPS_DEV
 
 int tips_fused_allreduce_host(const void* const* ins, void* const* outs, const int64_t* counts, int n, int dtype) {
-  TRY(check_dtype(dtype));
-  if (n < 0 || (n > 0 && (!ins || !outs || !counts))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  std::vector<BatchItem> items((size_t)n);
-  for (int i = 0; i < n; i++) {
-    if (counts[i] < 0 || (counts[i] > 0 && (!ins[i] || !outs[i]))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor %d", i);
-    items[i] = BatchItem{ins[i], outs[i], counts[i]};
-  }
-  int routed_rc;
-  int64_t shape[2] = {n, 0};
-  for (int i = 0; i < n; i++) shape[1] += counts[i];
-  if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 2, 0,
-                       [&] { return tips_fused_allreduce_host(ins, outs, counts, n, dtype); }, &routed_rc))
-    return routed_rc;
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  TRY(set_device(st));
-  for (int i = 0; i < n; i++)
-    if (items[i].count > 0 && (is_device_ptr(items[i].in) || is_device_ptr(items[i].out)))
-      return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host: tensor %d is in device memory", i);
-  return fused_allreduce_host(st, items.data(), n, dtype, nullptr);
+  return list_collective(
+      ins, counts, n, dtype, dtype, kOutsEach, outs, nullptr, true, [&](State& st, std::vector<BatchItem>& items) -> int {
+        for (int i = 0; i < n; i++)
+          if (items[i].count > 0 && (is_device_ptr(items[i].in) || is_device_ptr(items[i].out)))
+            return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host: tensor %d is in device memory", i);
+        return fused_allreduce_host(st, items.data(), n, dtype, nullptr);
+      });
 }
 
 int tips_fused_allreduce_host_flat(const void* const* ins, const int64_t* counts, int n, int dtype, void* flat) {
-  TRY(check_dtype(dtype));
-  if (n < 0 || (n > 0 && (!ins || !counts || !flat))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  std::vector<BatchItem> items((size_t)n);
-  for (int i = 0; i < n; i++) {
-    if (counts[i] < 0 || (counts[i] > 0 && !ins[i])) return fail(TIPS_ERR_INVALID_ARG, "bad tensor %d", i);
-    items[i] = BatchItem{ins[i], flat, counts[i]};
-  }
-  int routed_rc;
-  int64_t shape[2] = {n, 0};
-  for (int i = 0; i < n; i++) shape[1] += counts[i];
-  if (route_collective(TIPS_REQ_ALLREDUCE, dtype, shape, 2, 0,
-                       [&] { return tips_fused_allreduce_host_flat(ins, counts, n, dtype, flat); }, &routed_rc))
-    return routed_rc;
-  State& st = S();
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  if (n == 0) return 0;
-  TRY(set_device(st));
-  if (is_device_ptr(flat)) return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host_flat: flat is device memory");
-  for (int i = 0; i < n; i++)
-    if (items[i].count > 0 && is_device_ptr(items[i].in))
-      return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host_flat: tensor %d is in device memory", i);
-  return fused_allreduce_host(st, items.data(), n, dtype, (char*)flat);
+  return list_collective(
+      ins, counts, n, dtype, dtype, kOutsFlat, nullptr, flat, true, [&](State& st, std::vector<BatchItem>& items) -> int {
+        if (is_device_ptr(flat)) return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host_flat: flat is device memory");
+        for (int i = 0; i < n; i++)
+          if (items[i].count > 0 && is_device_ptr(items[i].in))
+            return fail(TIPS_ERR_INVALID_ARG, "tips_fused_allreduce_host_flat: tensor %d is in device memory", i);
+        return fused_allreduce_host(st, items.data(), n, dtype, (char*)flat);
+      });
 }
 
 int tips_host_register(void* ptr, int64_t bytes) {

@@ -347,6 +347,16 @@ int negotiation_stop();
 // run directly (no negotiation, or already on the negotiation thread).
 bool route_collective(int type, int dtype, const int64_t* shape, int ndim, int root, const std::function<int()>& body,
                       int* rc);
+// fusion.cc: how every tensor-list entry point opens. Checks `dtype` and the list, builds the items
+// (out[i] = outs[i], the input itself, or `flat` for every tensor), routes the call as an allreduce
+// of `announce` and shape [n, elements] (route_collective; `route` false: never), and runs
+// body(st, items) holding st.mu after the device is set. Not initialised is reported before n == 0
+// (which returns 0 without the body); a routed body runs on the negotiation thread without a
+// second validation.
+enum ListOuts { kOutsEach, kOutsNone, kOutsFlat };
+using ListBody = std::function<int(State&, std::vector<BatchItem>&)>;
+int list_collective(const void* const* ins, const int64_t* counts, int n, int dtype, int announce, ListOuts kind,
+                    void* const* outs, void* flat, bool route, const ListBody& body);
 // Whether the calling thread is a negotiation thread (named requests and routed calls execute there)
 bool on_negotiation_thread();
 
