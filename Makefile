@@ -6,11 +6,11 @@ ARCH     ?= gfx950
 LIB      := tips_amd/lib/libtips_hip.so
 SRCS     := tips_amd/csrc/kernels.hip tips_amd/csrc/runtime.cc tips_amd/csrc/rt_common.cc tips_amd/csrc/plan.cc tips_amd/csrc/schedules.cc \
             tips_amd/csrc/fusion.cc tips_amd/csrc/host_staging.cc tips_amd/csrc/control.cc tips_amd/csrc/negotiate.cc tips_amd/csrc/peer.cc \
-            tips_amd/csrc/bootstrap.cc
+            tips_amd/csrc/bootstrap.cc tips_amd/csrc/neg_protocol.cc tips_amd/csrc/err.cc
 # the tuning sweeps' kernels: the development and sanitizer libraries only
 DEV_SRCS := tips_amd/csrc/kernels_dev.hip
 HDRS     := tips_amd/csrc/kernels.h tips_amd/csrc/kernels_device.h tips_amd/csrc/kernels_dev.h tips_amd/csrc/rt.h tips_amd/csrc/net.h tips_amd/csrc/plan.h include/tips_hip.h \
-            include/tips_hip_dev.h
+            include/tips_hip_dev.h tips_amd/csrc/err.h tips_amd/csrc/neg_protocol.h
 DEVLIB   := tools/lib/libtips_hip_dev.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-result -fvisibility=hidden
 
@@ -23,7 +23,7 @@ FAST     := tips_amd/_fast$(shell python3 -c "import sysconfig; print(sysconfig.
 TORCH    := $(shell python3 -c "import os, torch; print(os.path.dirname(torch.__file__))" 2>/dev/null)
 PYINC    := $(shell python3 -c "import sysconfig; print(sysconfig.get_paths()['include'])")
 
-all: $(LIB) $(DEVLIB) $(FAST) $(CRASH) $(REPRO) oracle tsan tools/cpu_sum_bench
+all: $(LIB) $(DEVLIB) $(FAST) $(CRASH) $(REPRO) oracle tsan tools/cpu_sum_bench tools/_bin/neg_protocol_check
 
 # the Python mirror's list helper (tips_amd._fast: tensor pointers / counts in C++), torch headers
 $(FAST): tips_amd/csrc/pyfast.cc
@@ -100,6 +100,14 @@ tools/_bin/op_host_check: tools/op_host.c $(LIB) include/tips_hip.h oracle/build
 	gcc -O2 -std=gnu11 -Wall -DOP_HOST_ORACLE -Iinclude -Ioracle -o $@ $< -Ltips_amd/lib -ltips_hip -Loracle/build -loracle \
 	  -lpthread -Wl,-rpath,'$$ORIGIN/../../tips_amd/lib' -Wl,-rpath,'$$ORIGIN/../../oracle/build'
 
+# the negotiation's protocol unit on its own, under AddressSanitizer and UBSan (tests/test_neg_protocol.py):
+# the host compiler and these two sources only - that it links without HIP or RCCL is part of the check
+tools/_bin/neg_protocol_check: tests/c/neg_protocol_check.cc tips_amd/csrc/neg_protocol.cc tips_amd/csrc/err.cc \
+                               tips_amd/csrc/neg_protocol.h tips_amd/csrc/err.h include/tips_hip.h
+	@mkdir -p tools/_bin
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan \
+	  -o $@ $(filter %.cc,$^)
+
 oracle/build/liboracle.so: oracle/oracle.c oracle/oracle.h
 	$(MAKE) -C oracle build/liboracle.so
 
@@ -156,7 +164,7 @@ tools/sum_sweep: tools/sum_sweep.cc $(DEVLIB)
 
 clean:
 	rm -rf build/obj build/dev
-	rm -f $(LIB) $(DEVLIB) $(REPRO) tools/sum_sweep tools/cpu_sum_bench tools/peer_mem_probe tools/ipc_probe
+	rm -f $(LIB) $(DEVLIB) $(REPRO) tools/_bin/neg_protocol_check tools/sum_sweep tools/cpu_sum_bench tools/peer_mem_probe tools/ipc_probe
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle tools repro clean tsan

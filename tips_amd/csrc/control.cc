@@ -3,7 +3,7 @@
 // Replaces the reference's rank-0 negotiation checks (ConstructResponseMessage,
 // tips/core/collective/coordinator.cc:90-186; GatherFirstRankSizes :40-88)
 // with one small RCCL exchange of request records, after which every rank
-// applies the same rules (so every rank reaches the same verdict); and the
+// applies the same rules (check_records, neg_protocol.cc; so every rank reaches the same verdict); and the
 // broadcast / allgatherv collectives (utils.h:83-134, ops.cc:156-286).
 #include <algorithm>
 #include <vector>
@@ -41,52 +41,6 @@ int exchange_i64(State& st, const int64_t* mine, int words, std::vector<int64_t>
 }
 
 }  // namespace
-
-std::string shape_str(const int64_t* rec) {  // tensorflow::TensorShape::DebugString() form: [2,4]
-  std::string s = "[";
-  for (int64_t d = 0; d < rec[2]; d++) s += (d ? "," : "") + std::to_string(rec[3 + d]);
-  return s + "]";
-}
-
-// ConstructResponseMessage (coordinator.cc:90-186) + GatherFirstRankSizes (:40-88): every
-// record is compared with rank 0's; the first mismatch is reported with the reference's text.
-int check_records(const int64_t* t, int p) {
-  const int W = TIPS_REQUEST_WORDS;
-  const int64_t* r0 = t;
-  for (int i = 1; i < p; i++)
-    if (t[i * W + 1] != r0[1])
-      return fail(TIPS_ERR_MISMATCH, "Mismatch data types found: %lld vs %lld.", (long long)r0[1], (long long)t[i * W + 1]);
-  for (int i = 1; i < p; i++)  // (the reference compares requests[0] with itself here, coordinator.cc:123-129)
-    if (t[i * W + 0] != r0[0])
-      return fail(TIPS_ERR_MISMATCH, "Mismatched operations found: %lld vs %lld.", (long long)r0[0], (long long)t[i * W]);
-  for (int i = 0; i < p; i++)
-    if (t[i * W + 2] < 0 || t[i * W + 2] > TIPS_MAX_DIMS) return fail(TIPS_ERR_INVALID_ARG, "bad ndim in request %d", i);
-  if (r0[0] == TIPS_REQ_ALLREDUCE || r0[0] == TIPS_REQ_BROADCAST) {
-    for (int i = 1; i < p; i++) {
-      const int64_t* ri = t + i * W;
-      bool same = ri[2] == r0[2];
-      for (int64_t d = 0; same && d < r0[2]; d++) same = ri[3 + d] == r0[3 + d];
-      if (!same)
-        return fail(TIPS_ERR_MISMATCH, "Mismatched %s tensor shapes: %s vs %s",
-                    r0[0] == TIPS_REQ_BROADCAST ? "broadcast" : "allreduce", shape_str(r0).c_str(), shape_str(ri).c_str());
-    }
-  } else if (r0[0] == TIPS_REQ_ALLGATHER) {
-    if (r0[2] == 0) return fail(TIPS_ERR_MISMATCH, "An empty tensor found");
-    for (int i = 1; i < p; i++) {
-      const int64_t* ri = t + i * W;
-      if (ri[2] != r0[2])
-        return fail(TIPS_ERR_MISMATCH, "Mismatched allgather tensor shapes: rank %lld vs %lld", (long long)r0[2],
-                    (long long)ri[2]);
-      for (int64_t d = 1; d < r0[2]; d++)
-        if (ri[3 + d] != r0[3 + d])
-          return fail(TIPS_ERR_MISMATCH, "Mismatched allgather tensor shapes: %lld-th dimension %lld vs %lld",
-                      (long long)d, (long long)r0[3 + d], (long long)ri[3 + d]);
-    }
-  } else {
-    return fail(TIPS_ERR_INVALID_ARG, "Not supported request type: %lld", (long long)r0[0]);
-  }
-  return 0;
-}
 
 }  // namespace rt
 }  // namespace tips

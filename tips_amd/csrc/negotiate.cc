@@ -3,8 +3,8 @@
 // Replaces the reference's coordinator (tips/core/collective/coordinator.cc):
 //   EnqueueTensorCollective (:223-241)  -> tips_enqueue_allreduce
 //   BackgroundThreadLoop (:355-513)     -> Negotiator::loop
-//   IncreTensorCount (:15-38)           -> Table::announce (per-name ready count)
-//   ConstructResponseMessage (:90-186)  -> check_records (control.cc), same error text
+//   IncreTensorCount (:15-38)           -> Table::announce (per-name ready count; neg_protocol.cc)
+//   ConstructResponseMessage (:90-186)  -> check_records (neg_protocol.cc), same error text
 //   PerformCollectiveOp (:243-353)      -> execute(): allreduce_device on the request's stream
 // TF runs ops in different orders on different ranks, so every rank must agree
 // on WHICH named tensors are ready everywhere and in WHAT order to reduce them.
@@ -15,6 +15,8 @@
 // every name all ranks have announced, and answers with the list to run; every
 // rank then reduces that list in that order on the owning request's stream.
 // Only control records travel here; tensor bytes go over RCCL / xGMI.
+// This file has the threads, the sockets and the HIP side; the records, rank 0's decision and the
+// response cache are neg_protocol.h's.
 //
 // Dry-run mode (tips_negotiation_selftest) runs the same protocol with an
 // executor that only logs the order, so it is testable across processes on a
@@ -29,6 +31,7 @@
 #include <memory>
 #include <thread>
 
+#include "neg_protocol.h"
 #include "net.h"
 #include "rt.h"
 
@@ -78,6 +81,9 @@ class AdaptiveMutex {
   pthread_mutex_t m_;
 };
 
+// Req::state (tips_debug_state prints the number)
+enum : int { kFailed = -1, kQueued = 0, kAnnounced = 1, kLaunched = 2 /* ev recorded */, kDone = 3 /* host / dry run / routed */ };
+
 struct Req {
   int64_t handle = 0;
   std::string name;
@@ -96,7 +102,8 @@ struct Req {
   hipStream_t stream = nullptr;
   hipEvent_t ev = nullptr;
   std::shared_ptr<GroupEv> gev;  // set when the request ran inside a fused batch (then ev is unused)
-  int state = 0;  // 0 queued, 1 announced, 2 launched (ev recorded), 3 done (host / dry run / routed), -1 error
+  int state = kQueued;
+  bool resolved() const { return state >= kLaunched || state == kFailed; }
   int code = TIPS_ERR_MISMATCH;  // the failure's status (a routed collective's own; a negotiation error's)
   std::string err;
   // A synchronous collective routed through the negotiation (route_collective): its body runs on
@@ -116,8 +123,7 @@ struct Req {
   std::string bad;
 };
 
-// Request handles, process-wide (per-thread blocks of 256: Negotiator::prepare); the submission
-// stack shard of each enqueuing thread (Negotiator::enqueue)
+// The submission stack shard of each enqueuing thread (Negotiator::enqueue)
 std::atomic<uint64_t> g_next_shard{0};
 // Request handles, process-wide (per-thread blocks of 256: Negotiator::prepare)
 std::atomic<int64_t> g_next_handle{0};
@@ -162,199 +168,31 @@ struct PtrRanges {
   }
 };
 
-// ---- wire format: flat little-endian records ----------------------------------
-struct Writer {
-  std::string b;
-  template <class T>
-  void put(T v) {
-    b.append(reinterpret_cast<const char*>(&v), sizeof v);
-  }
-  void str(const std::string& s) {
-    put<uint32_t>((uint32_t)s.size());
-    b += s;
-  }
-};
-
-struct Reader {
-  const std::string& b;
-  size_t off = 0;
-  bool ok = true;
-  explicit Reader(const std::string& s) : b(s) {}
-  template <class T>
-  T get() {
-    T v{};
-    if (off + sizeof v > b.size()) {
-      ok = false;
-      return v;
-    }
-    memcpy(&v, b.data() + off, sizeof v);
-    off += sizeof v;
-    return v;
-  }
-  std::string str() {
-    std::string s;
-    str_into(s);
-    return s;
-  }
-  void str_into(std::string& s) {  // (into a reused string: no allocation once its capacity fits)
-    const uint32_t n = get<uint32_t>();
-    if (!ok || off + n > b.size()) {
-      ok = false;
-      s.clear();
-      return;
-    }
-    s.assign(b.data() + off, n);
-    off += n;
-  }
-};
-
-// announce (rank -> rank 0): u8 shutdown, u32 n,
-//   n x {i32 type, i32 root, i32 dtype, i64 count, u32 ndim, ndim x i64 dim, str name}
-//   (the fields of the reference's RequestMessage, collective_messages.fbs: request type, dtype,
-//   name, shape; plus the broadcast root, which the reference never sends)
-// response (rank 0 -> all):  u8 shutdown, u32 n, n x {u8 ok, str name, str error, u32 m, m x i64 size}
-//   (sizes: an allgather's first dimension per rank, the ResponseMessage's tensor_sizes)
-struct Announce {
-  int type = TIPS_REQ_ALLREDUCE, root = 0;
-  bool bad = false;  // the announcing rank found the request unusable (its pointers disagree)
-  int dtype;
-  int64_t count;
-  std::vector<int64_t> shape;
-  std::string name;
-};
-
-struct Decision {
-  bool ok;
-  std::string name, err;
-  std::vector<int64_t> sizes;
-};
-
-// ---- rank 0's table (IncreTensorCount + ConstructResponseMessage) ---------------
-// A name joins the ready queue the moment its last rank announces it (or a
-// rank announces it twice), as IncreTensorCount feeds ready_to_reduce
-// (coordinator.cc:15-38, 451-455): rank 0's readiness order, O(1) per announce.
-struct Table {
-  struct Row {
-    std::vector<int64_t> rec;  // p records of TIPS_REQUEST_WORDS
-    std::vector<int> roots;    // broadcast root each rank named
-    std::vector<char> seen;
-    int nseen = 0;
-    bool queued = false;
-    std::string dup;  // set when a rank announced this name twice while unresolved
-    std::string bad;  // set when a rank announced this name as unusable (failed once all announced)
-  };
-  int p = 1;
-  std::unordered_map<std::string, Row> rows;
-  std::vector<std::string> ready_q;  // [0, nready): names that became ready (slots reused across cycles)
-  size_t nready = 0;
-  // Rows resolved in earlier cycles, kept with their map node, key and vectors: a new name reuses
-  // one instead of allocating all four (a 1000-gradient step resolves 1000 names a cycle).
-  std::vector<std::unordered_map<std::string, Row>::node_type> spare;
-
-  void announce(int rank, const Announce& a) {
-    auto it = rows.find(a.name);
-    if (it == rows.end()) {
-      if (!spare.empty()) {
-        auto nh = std::move(spare.back());
-        spare.pop_back();
-        nh.key() = a.name;
-        Row& r = nh.mapped();
-        r.rec.assign((size_t)p * TIPS_REQUEST_WORDS, 0);
-        r.seen.assign(p, 0);
-        r.roots.assign(p, 0);
-        r.nseen = 0;
-        r.queued = false;
-        r.dup.clear();
-        r.bad.clear();
-        it = rows.insert(std::move(nh)).position;
-      } else {
-        Row r;
-        r.rec.assign((size_t)p * TIPS_REQUEST_WORDS, 0);
-        r.seen.assign(p, 0);
-        r.roots.assign(p, 0);
-        it = rows.emplace(a.name, std::move(r)).first;
-      }
-    }
-    Row& r = it->second;
-    if (r.seen[rank]) {
-      if (r.dup.empty()) r.dup = "rank " + std::to_string(rank) + " enqueued " + a.name + " twice";
-    } else {
-      r.seen[rank] = 1;
-      r.nseen++;
-      if (a.bad && r.bad.empty())
-        r.bad = "named request " + a.name + ": one device and one host pointer on rank " + std::to_string(rank);
-      int64_t* rec = &r.rec[(size_t)rank * TIPS_REQUEST_WORDS];
-      rec[0] = a.type;
-      rec[1] = a.dtype;
-      r.roots[rank] = a.root;
-      rec[2] = (int64_t)a.shape.size();  // (<= TIPS_MAX_DIMS: checked at enqueue and on decode)
-      for (size_t d = 0; d < a.shape.size(); d++) rec[3 + d] = a.shape[d];
-    }
-    if (!r.queued && (!r.dup.empty() || r.nseen == p)) {
-      r.queued = true;
-      if (nready < ready_q.size()) ready_q[nready] = a.name;  // (assign into a kept string: no allocation)
-      else ready_q.push_back(a.name);
-      nready++;
-    }
-  }
-
-  // The names that became ready since the last call, in readiness order, each with its verdict,
-  // written straight into rank 0's response (ok, name, error, allgather sizes): no per-name
-  // Decision objects on the way. Returns how many.
-  uint32_t write_ready(Writer& w) {
-    const int W = TIPS_REQUEST_WORDS;
-    for (size_t q = 0; q < nready; q++) {
-      const std::string& name = ready_q[q];
-      auto it = rows.find(name);
-      Row& r = it->second;
-      const std::string* err = &r.dup;
-      std::string why;
-      bool ok = false;
-      if (r.dup.empty() && !r.bad.empty()) {
-        err = &r.bad;
-      } else if (r.dup.empty()) {
-        ok = check_records(r.rec.data(), p) == 0;
-        if (!ok) why = last_error();
-        if (ok && r.rec[0] == TIPS_REQ_BROADCAST)
-          for (int i = 1; i < p && ok; i++)
-            if (r.roots[i] != r.roots[0]) {
-              ok = false;
-              why = "Mismatched broadcast root ranks: " + std::to_string(r.roots[0]) + " vs " + std::to_string(r.roots[i]);
-            }
-        err = &why;
-      }
-      w.put<uint8_t>(ok ? 1 : 0);
-      w.str(name);
-      w.str(ok ? std::string() : *err);
-      if (ok && r.rec[0] == TIPS_REQ_ALLGATHER) {  // GatherFirstRankSizes (coordinator.cc:40-88)
-        w.put<uint32_t>((uint32_t)p);
-        for (int i = 0; i < p; i++) w.put<int64_t>(r.rec[(size_t)i * W + 3]);
-      } else {
-        w.put<uint32_t>(0);
-      }
-      if (spare.size() < 4096) spare.push_back(rows.extract(it));
-      else rows.erase(it);
-    }
-    const uint32_t n = (uint32_t)nready;
-    nready = 0;
-    return n;
-  }
-};
-
-// The name table's key carries the name's hash, made by the enqueuing thread (Req::name_hash): the
-// negotiation thread admits a request without reading the name's bytes, which another core wrote
-// (an insertion compares the cached hash first, the strings only when the hashes are equal).
-struct NameKey {
-  uint64_t h;
-  std::string s;
-  bool operator==(const NameKey& o) const { return h == o.h && s == o.s; }
-};
-struct NameKeyHash {
-  size_t operator()(const NameKey& k) const { return (size_t)k.h; }
-};
 using NameMap = std::unordered_map<NameKey, std::shared_ptr<Req>, NameKeyHash>;
 using HandleMap = std::unordered_map<int64_t, std::shared_ptr<Req>>;
 
+// What an enqueue asks for: what every request says of itself, and the rest for who sets it.
+struct ReqSpec {
+  ReqSpec(const char* name, const int64_t* shape, int ndim, int dtype, const void* in = nullptr, void* out = nullptr,
+          void* stream = nullptr)
+      : name(name), in(in), out(out), shape(shape), ndim(ndim), dtype(dtype), stream((hipStream_t)stream) {}
+  const char* name;
+  const void* in;
+  void* out;
+  const int64_t* shape;
+  int ndim, dtype;
+  hipStream_t stream;
+  int type = TIPS_REQ_ALLREDUCE;
+  int root = 0;                   // broadcast
+  tips_alloc_fn alloc = nullptr;  // allgather
+  void* actx = nullptr;
+  int64_t* out_rows = nullptr;
+  std::function<int()> body;    // a routed synchronous collective (route_collective)
+  tips_done_fn cb = nullptr;    // tips_enqueue_allreduce_cb: the callback travels with the request
+  void* cb_ctx = nullptr;
+};
+
+const char* const kNotRunning = "negotiation thread is not running";
 
 // Where the negotiation's threads run (1000 named requests at one rank took
 // 0.40 or 0.87-1.85 us per tensor, bimodal across processes on one box). The caller, the negotiation
@@ -446,7 +284,6 @@ class Negotiator {
     size_ = size;
     dry_ = dry_run;
     timeout_ms_ = timeout_s * 1000;
-    table_.p = size;
     by_name_.reserve(4096);  // (no rehash under the lock for a few thousand requests in flight)
     by_handle_.reserve(4096);
     std::string err;
@@ -553,6 +390,9 @@ class Negotiator {
         }
       }
     }
+    // TIPS_RESPONSE_CACHE=0: announce every request in full (A/B; every rank keeps the cache's
+    // bookkeeping either way, so ranks may differ in this setting)
+    own_.reset(new LoopOwn(size, env_i64("TIPS_RESPONSE_CACHE", 1) != 0));
     lockfree_ = env_i64("TIPS_ENQUEUE_LOCKFREE", 1) != 0;
     running_ = true;
     accepting_.store(true, std::memory_order_release);
@@ -583,32 +423,34 @@ class Negotiator {
   // Everything of an enqueue that needs no lock: the request, where its memory lives, its two
   // table entries (allocated here: executor threads enqueue at once, and the lock's hold time, not
   // the work, bounded them - 4 threads enqueueing config 5 were no faster than one).
-  int prepare(Prepared& p, const std::string& name, const void* in, void* out, const int64_t* shape, int ndim,
-              int dtype, hipStream_t s, int type, int root, tips_alloc_fn alloc, void* actx, int64_t* out_rows,
-              std::function<int()> body, PtrRanges* pr, bool handle_entry = true) {
-    if (ndim < 0 || ndim > TIPS_MAX_DIMS) return fail(TIPS_ERR_INVALID_ARG, "bad ndim %d", ndim);
-    if (type == TIPS_REQ_ALLGATHER && ndim < 1) return fail(TIPS_ERR_INVALID_ARG, "An empty tensor found");
+  // pr: the list call's known device allocations (PtrRanges), or none.
+  int prepare(Prepared& p, ReqSpec& q, PtrRanges* pr = nullptr) {
+    if (q.ndim < 0 || q.ndim > TIPS_MAX_DIMS) return fail(TIPS_ERR_INVALID_ARG, "bad ndim %d", q.ndim);
+    if (q.type == TIPS_REQ_ALLGATHER && q.ndim < 1) return fail(TIPS_ERR_INVALID_ARG, "An empty tensor found");
     auto r = std::make_shared<Req>();
-    r->body = std::move(body);
-    r->name = name;
-    r->name_hash = std::hash<std::string>()(name);
-    r->type = type;
-    r->root = root;
-    r->alloc = alloc;
-    r->actx = actx;
-    r->out_rows = out_rows;
-    r->in = in;
-    r->out = out;
+    r->body = std::move(q.body);
+    r->name = q.name;
+    r->name_hash = std::hash<std::string>()(r->name);
+    r->type = q.type;
+    r->root = q.root;
+    r->alloc = q.alloc;
+    r->actx = q.actx;
+    r->out_rows = q.out_rows;
+    r->in = q.in;
+    r->out = q.out;
     r->count = 1;
-    r->shape.reserve((size_t)std::max(ndim, 1));
-    for (int d = 0; d < ndim; d++) {
-      if (shape[d] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative dimension");
-      r->shape.push_back(shape[d]);
-      r->count *= shape[d];
+    r->shape.reserve((size_t)std::max(q.ndim, 1));
+    for (int d = 0; d < q.ndim; d++) {
+      if (q.shape[d] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative dimension");
+      r->shape.push_back(q.shape[d]);
+      r->count *= q.shape[d];
     }
-    if (ndim == 0) r->shape.push_back(1);  // a scalar travels as shape [1] (CreateNoEmptyTfShape, coordinator.cc:212-221)
-    r->dtype = dtype;
-    r->stream = s;
+    if (q.ndim == 0) r->shape.push_back(1);  // a scalar travels as shape [1] (CreateNoEmptyTfShape, coordinator.cc:212-221)
+    r->dtype = q.dtype;
+    r->stream = q.stream;
+    r->cb = q.cb;  // (one lock, as OpRecord)
+    r->cb_ctx = q.cb_ctx;
+    r->cb_only = q.cb != nullptr;
     if (!dry_ && !r->body && r->count > 0) {  // the real executor (the dry run touches no memory; a routed body checks its own)
       // device tensors run stream-ordered on `s`; host tensors (the reference's MPIAllreduce is a
       // CPU op, ops.cc:118) run synchronously on the executor thread, staged through HBM as
@@ -619,8 +461,8 @@ class Negotiator {
       PtrRanges one;
       if (!pr && at_enqueue) pr = &one;
       if (pr) {
-        const bool din = pr->is_device(in), dout = type == TIPS_REQ_ALLGATHER ? din : pr->is_device(out);
-        if (din != dout) return fail(TIPS_ERR_INVALID_ARG, "named request %s: one device and one host pointer", name.c_str());
+        const bool din = pr->is_device(q.in), dout = q.type == TIPS_REQ_ALLGATHER ? din : pr->is_device(q.out);
+        if (din != dout) return fail(TIPS_ERR_INVALID_ARG, "named request %s: one device and one host pointer", q.name);
         r->host = !din;
       } else {
         r->classify = true;
@@ -637,9 +479,9 @@ class Negotiator {
     }
     thread_local NameMap name_scratch;
     thread_local HandleMap handle_scratch;
-    name_scratch.emplace(NameKey{r->name_hash, name}, r);
+    name_scratch.emplace(NameKey{r->name_hash, r->name}, r);
     p.name_node = name_scratch.extract(name_scratch.begin());
-    if (handle_entry) {  // (a request enqueued with its callback has none: nothing looks it up)
+    if (!q.cb) {  // (a request enqueued with its callback has no handle entry: nothing looks it up)
       handle_scratch.emplace(r->handle, r);
       p.handle_node = handle_scratch.extract(handle_scratch.begin());
     }
@@ -650,33 +492,43 @@ class Negotiator {
   // Under m_: the request's table entries and the fresh queue. The handle, or < 0. (Its completion
   // event, if it ever needs one, is taken when it runs: take_event.)
   int64_t commit(Prepared& p) {
-    Req& r = *p.r;
-    if (!running_) return fail(TIPS_ERR_NOT_INITIALIZED, "negotiation thread is not running");
-    if (!by_name_.insert(std::move(p.name_node)).inserted)
-      return fail(TIPS_ERR_INVALID_ARG, "a request named %s is already pending", r.name.c_str());
-    if (p.handle_node) by_handle_.insert(std::move(p.handle_node));
-    admit(std::move(p.r));
-    return r.handle;
+    const int64_t h = p.r->handle;
+    std::string why;
+    const int rc = admit_prepared(p, false, &why, [](int) {});
+    return rc ? fail(rc, "%s", why.c_str()) : h;
   }
 
-  int64_t enqueue(const std::string& name, const void* in, void* out, const int64_t* shape, int ndim, int dtype,
-                  hipStream_t s, int type = TIPS_REQ_ALLREDUCE, int root = 0, tips_alloc_fn alloc = nullptr,
-                  void* actx = nullptr, int64_t* out_rows = nullptr, std::function<int()> body = nullptr,
-                  PtrRanges* pr = nullptr, tips_done_fn cb = nullptr, void* cb_ctx = nullptr) {
-    Prepared p;
-    TRY(prepare(p, name, in, out, shape, ndim, dtype, s, type, root, alloc, actx, out_rows, std::move(body), pr,
-                cb == nullptr));
-    if (cb) {  // tips_enqueue_allreduce_cb: the callback travels with the request (one lock, as OpRecord)
-      p.r->cb = cb;
-      p.r->cb_ctx = cb_ctx;
-      p.r->cb_only = true;
+  // (m_ held) One prepared request into the two tables and the next announce (admit): 0, or the
+  // refusal's status with its reason in *why; nothing is queued then, and the request keeps its
+  // handle entry only if `handle_anyway` (a drained request fails through its handle, a committed
+  // one at its enqueue). lap: the trace's admission phases.
+  template <class Lap>
+  int admit_prepared(Prepared& p, bool handle_anyway, std::string* why, Lap lap) {
+    int code = 0;
+    if (!running_) {
+      *why = kNotRunning;
+      code = TIPS_ERR_NOT_INITIALIZED;
+    } else if (!by_name_.insert(std::move(p.name_node)).inserted) {
+      *why = "a request named " + p.r->name + " is already pending";
+      code = TIPS_ERR_INVALID_ARG;
     }
+    lap(1);
+    if (p.handle_node && (code == 0 || handle_anyway)) by_handle_.insert(std::move(p.handle_node));
+    lap(2);
+    if (code == 0) admit(std::move(p.r));
+    return code;
+  }
+
+  int64_t enqueue(ReqSpec& q) {
+    const bool cb = q.cb != nullptr;
+    Prepared p;
+    TRY(prepare(p, q));
     // (no st.mu: the executor holds it while it reduces, and nothing here needs it)
     if (cb && !waiter_started_.load(std::memory_order_acquire)) {
       std::lock_guard<AdaptiveMutex> l(m_);
       // (only while running: a waiter started after stop() joined the last one is never joined,
       // and the negotiator's destructor would end the process on it - ADVICE r05)
-      if (!running_ || waiter_stop_) return fail(TIPS_ERR_NOT_INITIALIZED, "negotiation thread is not running");
+      if (!running_ || waiter_stop_) return fail(TIPS_ERR_NOT_INITIALIZED, "%s", kNotRunning);
       start_waiter_locked();
     }
     if (!lockfree_) {  // (TIPS_ENQUEUE_LOCKFREE=0: round 4's locked commit, for A/B runs only)
@@ -689,8 +541,7 @@ class Negotiator {
       }
       return h;
     }
-    if (!accepting_.load(std::memory_order_acquire))
-      return fail(TIPS_ERR_NOT_INITIALIZED, "negotiation thread is not running");
+    if (!accepting_.load(std::memory_order_acquire)) return fail(TIPS_ERR_NOT_INITIALIZED, "%s", kNotRunning);
     const int64_t h = p.r->handle;
     static std::atomic<int64_t> gap_us{-1};  // (tests: TIPS_TEST_ENQUEUE_GAP_US widens the check-to-push window)
     int64_t gap = gap_us.load(std::memory_order_relaxed);
@@ -789,20 +640,8 @@ class Negotiator {
         Prepared& p = q->p;
         Req& r = *p.r;
         std::string why;
-        int code = TIPS_ERR_INVALID_ARG;
-        if (!running_) {
-          why = "negotiation thread is not running";
-          code = TIPS_ERR_NOT_INITIALIZED;
-        }
-        if (why.empty() && !by_name_.insert(std::move(p.name_node)).inserted)
-          why = "a request named " + r.name + " is already pending";
-        lap(1);
-        if (p.handle_node) by_handle_.insert(std::move(p.handle_node));
-        lap(2);
-        if (why.empty()) {
-          admit(std::move(p.r));
-        } else {
-          r.state = -1;
+        if (const int code = admit_prepared(p, true, &why, lap)) {
+          r.state = kFailed;
           r.code = code;
           r.err = why;
           if (r.cb) {
@@ -823,7 +662,7 @@ class Negotiator {
 
   // (m_ held) A request joins the next announce; counted when the previous batch named it
   void admit(std::shared_ptr<Req>&& r) {
-    if (!expect_.empty() && std::binary_search(expect_.begin(), expect_.end(), r->name_hash)) expect_hits_++;
+    expect_.admitted(r->name_hash);
     fresh_.push_back(std::move(r));
   }
 
@@ -864,29 +703,43 @@ class Negotiator {
       if (it == by_handle_.end()) return fail(TIPS_ERR_INVALID_ARG, "unknown request handle %lld", (long long)h);
       r = it->second;
       if (r->cb) return fail(TIPS_ERR_INVALID_ARG, "request %s completes through its callback (tips_on_done)", r->name.c_str());
-      if (block) cv_.wait(l, [&] { return r->state >= 2 || r->state < 0; });
-      if (r->state == 0 || r->state == 1) return 0;
+      if (block) cv_.wait(l, [&] { return r->resolved(); });
+      if (!r->resolved()) return 0;
     }
     int rc = 1;
-    if (r->state < 0) {
+    if (r->state == kFailed) {
       rc = fail(r->code, "%s", r->err.c_str());
-    } else if (r->state == 2 && !routed && !(r->gev && r->gev->done.load(std::memory_order_acquire))) {
-      hipEvent_t ev = r->gev ? r->gev->ev : r->ev;
-      hipError_t e = block ? hipEventSynchronize(ev) : hipEventQuery(ev);
+    } else if (r->state == kLaunched && !routed && !event_done(*r)) {
+      const hipError_t e = finish_event(*r, block);
       if (e == hipErrorNotReady) return 0;
       if (e != hipSuccess) rc = fail(TIPS_ERR_HIP, "request %s: %s", r->name.c_str(), hipGetErrorString(e));
-      else if (r->gev) r->gev->done.store(true, std::memory_order_release);
     }
-    release(h, r);
+    HandleMap::node_type gone;  // (freed after the lock)
+    {
+      std::lock_guard<AdaptiveMutex> l(m_);
+      gone = release_locked(*r);
+    }
     return rc;
   }
 
-  void release(int64_t h, const std::shared_ptr<Req>& r) {
-    std::lock_guard<AdaptiveMutex> l(m_);
-    if (r->ev) ev_pool_.push_back(r->ev);  // reused by the next request
-    r->ev = nullptr;
-    r->gev.reset();
-    by_handle_.erase(h);
+  // Whether a launched request's device work is known to be done without a HIP call (its fused
+  // batch's event was waited for already); else finish_event waits for (block) or queries its
+  // event, and marks the group done.
+  static bool event_done(const Req& r) { return r.gev && r.gev->done.load(std::memory_order_acquire); }
+  static hipError_t finish_event(Req& r, bool block) {
+    hipEvent_t ev = r.gev ? r.gev->ev : r.ev;
+    const hipError_t e = block ? hipEventSynchronize(ev) : hipEventQuery(ev);
+    if (e == hipSuccess && r.gev) r.gev->done.store(true, std::memory_order_release);
+    return e;
+  }
+
+  // (m_ held) A finished request gives up its event and leaves the handle table; its entry is
+  // returned to be freed outside the lock (enqueueing threads wait on it).
+  HandleMap::node_type release_locked(Req& r) {
+    if (r.ev) ev_pool_.push_back(r.ev);  // reused by the next request
+    r.ev = nullptr;
+    r.gev.reset();
+    return r.cb_only ? HandleMap::node_type() : by_handle_.extract(r.handle);
   }
 
   // tips_on_done: fn(ctx, status, message) is called once, from the completion thread, when the
@@ -900,13 +753,13 @@ class Negotiator {
     auto& r = it->second;
     if (r->cb) return fail(TIPS_ERR_INVALID_ARG, "request %s already has a completion callback", r->name.c_str());
     if (waiter_stop_) {  // (after stop: no completion thread will come; the request has finished)
-      fn(ctx, r->state < 0 ? r->code : 0, r->state < 0 ? r->err.c_str() : "");
+      fn(ctx, r->state == kFailed ? r->code : 0, r->state == kFailed ? r->err.c_str() : "");
       return 0;
     }
     r->cb = fn;
     r->cb_ctx = ctx;
     start_waiter_locked();
-    if (r->state >= 2 || r->state < 0) queue_done(r);
+    if (r->resolved()) queue_done(r);
     return 0;
   }
 
@@ -933,10 +786,10 @@ class Negotiator {
     return loop_err_.empty() ? 0 : fail(TIPS_ERR_BOOTSTRAP, "%s", loop_err_.c_str());
   }
 
-  // number of completion callbacks called so far (the selftest's log)
   // decisions that came back as "cached OK" (the response cache; read after stop())
   int64_t cached_decisions() const { return cached_decisions_.load(std::memory_order_relaxed); }
 
+  // number of completion callbacks called so far (the selftest's log)
   int64_t callbacks_called() {
     std::lock_guard<AdaptiveMutex> l(m_);
     return cb_called_;
@@ -974,9 +827,7 @@ class Negotiator {
     for (auto& r : orphans) r->cb(r->cb_ctx, r->code, r->err.c_str());
     for (auto& kv : by_handle_)  // never polled to completion
       if (kv.second->ev) ev_pool_.push_back(kv.second->ev);
-    for (hipEvent_t e : ev_pool_) (void)hipEventDestroy(e);
-    join_ev_.release();
-    if (neg_stream_) (void)hipStreamDestroy(neg_stream_);
+    release_device_resources();
   }
 
   bool running() {
@@ -1016,8 +867,7 @@ class Negotiator {
     const int64_t expect_quiet_ns = 1000 * std::max<int64_t>(0, env_i64("TIPS_LINGER_EXPECT_US", 4));
     // (the waits while the set is not complete are stepped, so its completion is seen within this)
     const int64_t expect_step_ns = 8000;
-    std::vector<std::shared_ptr<Req>> prev;  // the previous cycle's named requests
-    auto complete = [&] { return expect_on && !expect_.empty() && expect_hits_ == expect_.size(); };
+    auto complete = [&] { return expect_on && expect_.complete(); };
     // TIPS_NEG_TRACE=1: per cycle with requests, on stderr: the batch, and how long the linger, the
     // exchange with rank 0 and the execution took (microseconds)
     const bool trace = env_i64("TIPS_NEG_TRACE", 0) != 0;
@@ -1034,10 +884,7 @@ class Negotiator {
     std::vector<Decision> ds;
     std::vector<uint32_t> cids;
     std::vector<Req*> full;
-    // TIPS_RESPONSE_CACHE=0: announce every request in full (A/B; every rank keeps the cache's
-    // bookkeeping either way, so ranks may differ in this setting). Rank 0 counts ids in a 64-bit
-    // rank mask: above 64 ranks everything travels in full.
-    const bool send_ids = env_i64("TIPS_RESPONSE_CACHE", 1) != 0 && size_ <= 64;
+    ResponseCache& cache = own_->cache;
     while (true) {
       std::vector<std::shared_ptr<Req>> batch;
       bool stopping;
@@ -1091,7 +938,7 @@ class Negotiator {
               l.lock();
             } else {
               int64_t wait = std::min(need - quiet, cycle_ns - (now - start));
-              if (expect_on && !expect_.empty() && !done) wait = std::min(wait, expect_step_ns);
+              if (expect_on && !expect_.want.empty() && !done) wait = std::min(wait, expect_step_ns);
               const int64_t a = steady_ns();
               cv_.wait_for(l, std::chrono::nanoseconds(wait));
               wait_ns += steady_ns() - a;
@@ -1102,22 +949,10 @@ class Negotiator {
         batch.assign(fresh_.begin(), fresh_.end());
         fresh_.clear();
         if (expect_on) {  // the next cycle expects this one's names and the previous one's
-          std::vector<std::shared_ptr<Req>> cur;  // (routed ~sync requests are named per call: never expected)
-          for (auto& r : batch)
-            if (r->name.compare(0, 6, "~sync.") != 0) cur.push_back(r);
-          // (kept as it is when this cycle named exactly the expected set: the previous one's
-          // names are in it already)
-          if (!cur.empty() && !(expect_hits_ == expect_.size() && cur.size() == expect_.size())) {
-            expect_.clear();
-            for (auto& r : cur) expect_.push_back(r->name_hash);
-            for (auto& r : prev) expect_.push_back(r->name_hash);
-            std::sort(expect_.begin(), expect_.end());
-            expect_.erase(std::unique(expect_.begin(), expect_.end()), expect_.end());
-          }
-          if (!cur.empty()) prev.swap(cur);
-          expect_hits_ = 0;
+          for (auto& r : batch) expect_.roll_add(r->name, r->name_hash);
+          expect_.roll();
         }
-        for (auto& r : batch) r->state = 1;
+        for (auto& r : batch) r->state = kAnnounced;
         stopping = want_stop_;
         t_linger = us_since(t0);
         t_tail = (steady_ns() - last_arrival_ns_.load(std::memory_order_acquire)) / 1000;
@@ -1131,63 +966,30 @@ class Negotiator {
         }
       const auto t_x = std::chrono::steady_clock::now();
       w.b.clear();
-      w.put<uint8_t>(stopping ? 1 : 0);
       // a request the response cache holds with the same dtype and shape travels as its cache id
       // (4 bytes; rank 0 counts it without a name); the rest as full records
       cids.clear();
       full.clear();
       for (auto& r : batch) {
-        const int32_t id = send_ids ? cached_id(*r) : -1;
+        const int32_t id = cache.cached_id(r->name, r->name_hash, r->type, r->dtype, r->shape, !r->bad.empty());
         if (id >= 0) cids.push_back((uint32_t)id);
         else full.push_back(r.get());
       }
-      w.put<uint32_t>((uint32_t)full.size());
-      for (Req* r : full) {
-        w.put<int32_t>(r->type);
-        w.put<int32_t>(r->root);
-        w.put<uint8_t>(r->bad.empty() ? 0 : 1);
-        w.put<int32_t>(r->dtype);
-        w.put<int64_t>(r->count);
-        w.put<uint32_t>((uint32_t)r->shape.size());
-        for (int64_t d : r->shape) w.put<int64_t>(d);
-        w.str(r->name);
-      }
-      w.put<uint32_t>((uint32_t)cids.size());
-      for (uint32_t id : cids) w.put<uint32_t>(id);
+      put_announce_head(w, stopping, (uint32_t)full.size());
+      for (Req* r : full) put_announce_record(w, r->type, r->root, !r->bad.empty(), r->dtype, r->count, r->shape, r->name);
+      put_announce_ids(w, cids);
       set_phase("exchange (cycle " + std::to_string((long long)cycles_) + ", announcing " + std::to_string(batch.size()) + ")");
       if (!exchange(w.b, &resp)) break;
       {
         std::lock_guard<std::mutex> l(phase_mu_);
         cycles_++;
       }
-      Reader rd(resp);
-      const bool shutdown = rd.get<uint8_t>() != 0;
-      const uint32_t n = rd.get<uint32_t>();
+      bool shutdown = false;
       size_t nd = 0;
-      for (uint32_t i = 0; i < n && rd.ok; i++) {
-        if (nd == ds.size()) ds.emplace_back();
-        Decision& d = ds[nd++];  // (a kept slot: its strings keep their capacity)
-        const uint8_t tag = rd.get<uint8_t>();
-        d.sizes.clear();
-        d.err.clear();
-        if (tag == kCachedOk) {  // a cached allreduce every rank announced by id
-          const uint32_t id = rd.get<uint32_t>();
-          if (id >= cache_.size() || !cache_[id].live) {
-            rd.ok = false;
-            break;
-          }
-          d.ok = true;
-          d.name.assign(cache_[id].name);
-          cached_decisions_.fetch_add(1, std::memory_order_relaxed);
-          continue;
-        }
-        d.ok = tag != 0;
-        rd.str_into(d.name);
-        rd.str_into(d.err);
-        const uint32_t m = rd.get<uint32_t>();
-        for (uint32_t k = 0; k < m && rd.ok && k < (1u << 20); k++) d.sizes.push_back(rd.get<int64_t>());
-      }
-      if (!rd.ok) {
+      int64_t ncached = 0;
+      const bool wellformed = get_response(resp, cache, &shutdown, ds, &nd, &ncached);
+      cached_decisions_.fetch_add(ncached, std::memory_order_relaxed);
+      if (!wellformed) {
         set_loop_error("negotiation: malformed response");
         break;
       }
@@ -1199,7 +1001,7 @@ class Negotiator {
                 "ended %lld us after the latest arrival; waits %lld us, admissions %lld us, the last %d in %lld us), exchange %lld us "
                 "(rank 0's decision %lld us), execute %lld us\n", rank_, (long long)cycles_, batch.size(), nd, t_linger, windows,
                 t_tail, (long long)(wait_ns / 1000), (long long)(drain_ns / 1000), last_drained, (long long)(last_drain_ns / 1000),
-                t_exchange, (long long)(rank_ == 0 ? decide_ns_ / 1000 : -1), us_since(t_e));
+                t_exchange, (long long)(rank_ == 0 ? own_->decide_ns / 1000 : -1), us_since(t_e));
       if (trace && (!batch.empty() || nd)) {
         std::lock_guard<AdaptiveMutex> l(m_);
         fprintf(stderr, "[tips neg]   admission phases (us): walk %lld, name table %lld, handle table %lld, queue %lld, "
@@ -1218,7 +1020,7 @@ class Negotiator {
     std::sort(unmatched.begin(), unmatched.end());
     for (auto& name : unmatched) {  // never matched on every rank before the stop
       auto& r = by_name_.find(NameKey{std::hash<std::string>()(name), name})->second;
-      r->state = -1;
+      r->state = kFailed;
       r->code = TIPS_ERR_MISMATCH;
       r->err = "request " + name + " was not enqueued on every rank before shutdown";
       if (dry_) log_.push_back(name + " ERR " + r->err);
@@ -1238,7 +1040,7 @@ class Negotiator {
 
   // The completion thread: in the order requests finished, wait for a device request's work, call
   // its callback (without the lock: a callback may enqueue more requests) and release its handle.
-  // The completion thread: takes every queued request at once (a fused batch of host requests is
+  // It takes every queued request at once (a fused batch of host requests is
   // queued together: config 5's 214 in one go), runs each callback - for device work after its
   // event - and releases the batch's handles with one lock. Its phase for tips_debug_state is the
   // request it is at, formatted only when asked (a string per request cost ~1 ms per config-5 step).
@@ -1254,18 +1056,15 @@ class Negotiator {
       for (auto& r : batch) {
         int status = 0;
         std::string msg;
-        if (r->state < 0) {
+        if (r->state == kFailed) {
           status = r->code;
           msg = r->err;
-        } else if (r->state == 2 && !(r->gev && r->gev->done.load(std::memory_order_acquire))) {
+        } else if (r->state == kLaunched && !event_done(*r)) {
           set_waiter_req(r, true);
-          hipEvent_t ev = r->gev ? r->gev->ev : r->ev;
-          const hipError_t e = hipEventSynchronize(ev);
+          const hipError_t e = finish_event(*r, true);
           if (e != hipSuccess) {
             status = TIPS_ERR_HIP;
             msg = std::string("request ") + r->name + ": " + hipGetErrorString(e);
-          } else if (r->gev) {
-            r->gev->done.store(true, std::memory_order_release);
           }
         }
         set_waiter_req(r, false);
@@ -1276,12 +1075,7 @@ class Negotiator {
       gone.reserve(batch.size());
       {
         std::lock_guard<AdaptiveMutex> l(m_);
-        for (auto& r : batch) {  // (release() for the whole batch)
-          if (r->ev) ev_pool_.push_back(r->ev);
-          r->ev = nullptr;
-          r->gev.reset();
-          if (!r->cb_only) gone.push_back(by_handle_.extract(r->handle));
-        }
+        for (auto& r : batch) gone.push_back(release_locked(*r));
         cb_called_ += (int64_t)batch.size();
       }
       gone.clear();
@@ -1291,12 +1085,7 @@ class Negotiator {
 
   // One lockstep cycle: my announce goes up, rank 0's decision comes back.
   bool exchange(const std::string& mine, std::string* resp) {
-    if (size_ == 1) {
-      const int64_t a = steady_ns();
-      const bool ok = decide({mine}, resp);
-      decide_ns_ = steady_ns() - a;
-      return ok;
-    }
+    if (size_ == 1) return decide(&mine, resp);
     if (rank_ != 0) {
       if (!send_msg(up_, mine) || !recv_msg(up_, resp, timeout_ms_)) {
         set_loop_error("negotiation: lost rank 0");
@@ -1311,9 +1100,7 @@ class Negotiator {
         set_loop_error("negotiation: lost rank " + std::to_string(r));
         return false;
       }
-    const int64_t a = steady_ns();
-    if (!decide(all, resp)) return false;
-    decide_ns_ = steady_ns() - a;
+    if (!decide(all.data(), resp)) return false;
     for (int r = 1; r < size_; r++)
       if (!send_msg(peers_[r], *resp)) {
         set_loop_error("negotiation: lost rank " + std::to_string(r));
@@ -1322,149 +1109,13 @@ class Negotiator {
     return true;
   }
 
-  // rank 0: fold every rank's announce into the table, answer with the ready list
-  bool decide(const std::vector<std::string>& all, std::string* resp) {
-    bool everyone_stops = true;
-    for (int r = 0; r < (int)all.size(); r++) {
-      Reader rd(all[r]);
-      everyone_stops &= rd.get<uint8_t>() != 0;
-      const uint32_t n = rd.get<uint32_t>();
-      Announce a;  // (one, reused: its shape and name keep their allocations)
-      for (uint32_t i = 0; i < n && rd.ok; i++) {
-        a.shape.clear();
-        a.type = rd.get<int32_t>();
-        a.root = rd.get<int32_t>();
-        a.bad = rd.get<uint8_t>() != 0;
-        a.dtype = rd.get<int32_t>();
-        a.count = rd.get<int64_t>();
-        const uint32_t ndim = rd.get<uint32_t>();
-        if (ndim > TIPS_MAX_DIMS) rd.ok = false;
-        for (uint32_t d = 0; d < ndim && rd.ok; d++) a.shape.push_back(rd.get<int64_t>());
-        rd.str_into(a.name);
-        if (!rd.ok) break;
-        // a full record of a name others announced by id this round: theirs join the table too
-        if (!cache_ids_.empty()) {
-          const int32_t id = cache_lookup(a.name, std::hash<std::string>()(a.name));
-          if (id >= 0) to_table(id);
-        }
-        table_.announce(r, a);
-      }
-      const uint32_t k = rd.get<uint32_t>();
-      for (uint32_t i = 0; i < k && rd.ok; i++) {
-        const uint32_t id = rd.get<uint32_t>();
-        if (id >= cache_.size() || !cache_[id].live) {
-          rd.ok = false;
-          break;
-        }
-        if (idst_.size() < cache_.size()) idst_.resize(cache_.size());
-        IdState& st = idst_[id];
-        const uint64_t bit = 1ull << r;
-        if (st.table || (st.mask & bit)) {  // (a rank's second announce: the table names the duplicate)
-          to_table(id);
-          table_.announce(r, expand(id));
-          continue;
-        }
-        st.mask |= bit;
-        if (++st.n == (int)all.size()) {  // every rank, every one by id: ready, valid as cached
-          st.mask = 0;
-          st.n = 0;
-          id_ready_.push_back(id);
-        }
-      }
-      if (!rd.ok) {
-        set_loop_error("negotiation: malformed announce from rank " + std::to_string(r));
-        return false;
-      }
-    }
-    for (size_t q = 0; q < table_.nready; q++) {  // (decided now: later ids of these names count anew)
-      const int32_t id = idst_.empty() ? -1 : cache_lookup(table_.ready_q[q], std::hash<std::string>()(table_.ready_q[q]));
-      if (id >= 0 && (size_t)id < idst_.size()) idst_[id].table = false;
-    }
-    Writer w;
-    w.b.swap(*resp);  // (the previous response's buffer, reused)
-    w.b.clear();
-    w.put<uint8_t>(everyone_stops ? 1 : 0);
-    const size_t count_at = w.b.size();
-    w.put<uint32_t>(0);
-    uint32_t n = table_.write_ready(w);
-    for (uint32_t id : id_ready_) {  // after the table's: readiness order among themselves
-      w.put<uint8_t>(kCachedOk);
-      w.put<uint32_t>(id);
-    }
-    n += (uint32_t)id_ready_.size();
-    id_ready_.clear();
-    memcpy(&w.b[count_at], &n, sizeof n);
-    resp->swap(w.b);
-    return true;
-  }
-
-  // ---- response cache (rank-0 side and the shared bookkeeping) ----------------------------
-  // An allreduce decided OK is cached on every rank under an id: the position of its first OK
-  // decision in the response stream, which every rank reads in the same order (execute()), so the
-  // ids agree without being sent. A later request with that name, dtype and shape is announced
-  // by id; when every rank announced an id by id, rank 0 answers "cached OK" without the table:
-  // the checks ConstructResponseMessage makes (coordinator.cc:90-186) passed for exactly these
-  // parameters. Any full record of the name (changed shape, an unusable pointer, a rank with the
-  // cache off) sends the round's ids of that name through the table, which then checks and
-  // words every failure as before. A failure drops the name from the cache on every rank.
-  int32_t cache_lookup(const std::string& name, uint64_t h) {
-    cache_look_.h = h;
-    cache_look_.s.assign(name);
-    auto it = cache_ids_.find(cache_look_);
-    return it == cache_ids_.end() ? -1 : (int32_t)it->second;
-  }
-  int32_t cached_id(const Req& r) {
-    if (r.type != TIPS_REQ_ALLREDUCE || !r.bad.empty() || cache_ids_.empty()) return -1;
-    const int32_t id = cache_lookup(r.name, r.name_hash);
-    if (id < 0) return -1;
-    const CacheEntry& e = cache_[(size_t)id];
-    return e.dtype == r.dtype && e.shape == r.shape ? id : -1;
-  }
-  Announce expand(uint32_t id) {
-    const CacheEntry& e = cache_[id];
-    Announce a;
-    a.type = TIPS_REQ_ALLREDUCE;
-    a.dtype = e.dtype;
-    a.count = e.count;
-    a.shape = e.shape;
-    a.name = e.name;
-    return a;
-  }
-  // (rank 0) this round's announces of id go to the table from now on, the ones counted so far too
-  void to_table(int32_t id) {
-    if ((size_t)id >= idst_.size()) idst_.resize(cache_.size());
-    IdState& st = idst_[(size_t)id];
-    if (st.table) return;
-    st.table = true;
-    for (int q = 0; q < 64 && st.mask; q++)
-      if (st.mask & (1ull << q)) {
-        st.mask &= ~(1ull << q);
-        table_.announce(q, expand((uint32_t)id));
-      }
-    st.n = 0;
-  }
-  // (every rank, execute(), in response order) an OK allreduce joins the cache or refreshes its
-  // parameters; a failure leaves it
-  void cache_note(const Decision& d, const Req* r) {
-    if (d.name.compare(0, 6, "~sync.") == 0) return;  // (routed calls: a name per call)
-    const int32_t id = cache_lookup(d.name, std::hash<std::string>()(d.name));
-    if (!d.ok || !r || r->type != TIPS_REQ_ALLREDUCE) {
-      if (id >= 0) {
-        cache_[(size_t)id].live = false;
-        cache_ids_.erase(cache_look_);
-      }
-      return;
-    }
-    if (id >= 0) {
-      CacheEntry& e = cache_[(size_t)id];
-      e.dtype = r->dtype;
-      e.count = r->count;
-      e.shape = r->shape;
-      return;
-    }
-    if (cache_.size() >= kCacheCap) return;  // (full: later names travel in full, on every rank alike)
-    cache_ids_.emplace(NameKey{std::hash<std::string>()(d.name), d.name}, (uint32_t)cache_.size());
-    cache_.push_back(CacheEntry{d.name, r->dtype, r->count, r->shape, true});
+  // rank 0's decision (Coordinator::decide), timed for the trace
+  bool decide(const std::string* all, std::string* resp) {
+    const int64_t a = steady_ns();
+    const int bad_rank = own_->coord.decide(all, resp);
+    own_->decide_ns = steady_ns() - a;
+    if (bad_rank >= 0) set_loop_error("negotiation: malformed announce from rank " + std::to_string(bad_rank));
+    return bad_rank < 0;
   }
 
   // PerformCollectiveOp for one cycle's ready list, in rank 0's order. Readiness
@@ -1493,15 +1144,22 @@ class Negotiator {
       }
     }
     gone.clear();
-    for (size_t i = 0; i < n; i++) cache_note(ds[i], reqs[i].get());  // (every rank, this order)
+    for (size_t i = 0; i < n; i++) {  // (every rank, this order: the cache ids agree)
+      if (const Req* r = reqs[i].get()) {
+        const ReqParams rp{r->type, r->dtype, r->count, r->shape};
+        own_->cache.note(ds[i], &rp);
+      } else {
+        own_->cache.note(ds[i], nullptr);
+      }
+    }
     std::vector<int> state(n, 0), code(n, TIPS_ERR_MISMATCH);
     std::vector<std::string> msg(n);
     for (size_t i = 0; i < n; i++) {
-      state[i] = ds[i].ok ? (dry_ ? 3 : 2) : -1;
+      state[i] = ds[i].ok ? (dry_ ? kDone : kLaunched) : kFailed;
       msg[i] = ds[i].err;
     }
     auto failed = [&](size_t k, int rc) {
-      state[k] = -1;
+      state[k] = kFailed;
       code[k] = rc;
       msg[k] = last_error();
     };
@@ -1509,8 +1167,13 @@ class Negotiator {
       State& st = S();
       const bool fuse = env_i64("TIPS_NEGOTIATED_FUSION", 1) != 0;
       const int64_t threshold = fusion_threshold_bytes();
+      // request k can join a fused run of `dtype` allreduces, all in host memory or all on the device
+      auto joins = [&](size_t k, bool host, int dtype) {
+        return reqs[k] && state[k] == kLaunched && !reqs[k]->body && reqs[k]->type == TIPS_REQ_ALLREDUCE &&
+               reqs[k]->host == host && reqs[k]->dtype == dtype;
+      };
       for (size_t i = 0; i < n;) {
-        if (!reqs[i] || state[i] != 2) {
+        if (!reqs[i] || state[i] != kLaunched) {
           i++;
           continue;
         }
@@ -1524,7 +1187,7 @@ class Negotiator {
         if (reqs[i]->body) {  // a routed synchronous collective: its own call, here, in rank 0's order
           const int rc = reqs[i]->body();
           if (rc != 0) failed(i, rc);
-          else state[i] = 3;
+          else state[i] = kDone;
           i++;
           continue;
         }
@@ -1533,9 +1196,7 @@ class Negotiator {
           // a run of host allreduces of one dtype: one fused host call (page-locked pieces, H2D ->
           // allreduce -> D2H pipelined, unpacked into each output), not one staged call per tensor
           size_t j = i;
-          while (j < n && reqs[j] && state[j] == 2 && !reqs[j]->body && reqs[j]->type == TIPS_REQ_ALLREDUCE &&
-                 reqs[j]->host && reqs[j]->dtype == dtype)
-            j++;
+          while (j < n && joins(j, true, dtype)) j++;
           if (j - i >= 2) {
             std::vector<BatchItem> items;
             for (size_t k = i; k < j; k++) items.push_back(BatchItem{reqs[k]->in, reqs[k]->out, reqs[k]->count});
@@ -1547,7 +1208,7 @@ class Negotiator {
             }
             for (size_t k = i; k < j; k++) {
               if (rc != 0) failed(k, rc);
-              else state[k] = 3;
+              else state[k] = kDone;
             }
             i = j;
             continue;
@@ -1556,7 +1217,7 @@ class Negotiator {
         if (reqs[i]->type != TIPS_REQ_ALLREDUCE || reqs[i]->host) {  // broadcast / allgather / host: one at a time
           const int rc = run_other(*reqs[i], ds[i].sizes);
           if (rc != 0) failed(i, rc);
-          else if (reqs[i]->host) state[i] = 3;  // finished: the host call returned with out written
+          else if (reqs[i]->host) state[i] = kDone;  // finished: the host call returned with out written
           i++;
           continue;
         }
@@ -1565,8 +1226,7 @@ class Negotiator {
         const int64_t es = tips::dtype_size(dtype);
         size_t j = i;
         int64_t bytes = 0;
-        while (fuse && j < n && reqs[j] && state[j] == 2 && !reqs[j]->body && reqs[j]->type == TIPS_REQ_ALLREDUCE &&
-               !reqs[j]->host && reqs[j]->dtype == dtype && reqs[j]->count * es < threshold &&
+        while (fuse && j < n && joins(j, false, dtype) && reqs[j]->count * es < threshold &&
                round_up(bytes, kAlignBytes) + reqs[j]->count * es <= threshold) {
           bytes = round_up(bytes, kAlignBytes) + reqs[j]->count * es;
           j++;
@@ -1692,7 +1352,15 @@ class Negotiator {
   bool dry_ = false;
   int lfd_ = -1, up_ = -1;
   std::vector<int> peers_;
-  Table table_;
+  // The negotiation thread's own, no lock: this rank's response cache, rank 0's side of the
+  // protocol (only rank 0 calls it) and, for the trace, how long its last decision took.
+  struct LoopOwn {
+    ResponseCache cache;
+    Coordinator coord;
+    int64_t decide_ns = 0;
+    LoopOwn(int size, bool by_id) : cache(size, by_id), coord(size, cache) {}
+  };
+  std::unique_ptr<LoopOwn> own_;  // (made by start(), before the thread)
   std::thread thread_;
   AdaptiveMutex m_;
   std::condition_variable_any cv_;
@@ -1722,40 +1390,13 @@ class Negotiator {
   bool lockfree_ = true;           // (set in start(), before any enqueue)
   std::atomic<bool> waiter_started_{false};
   std::deque<std::shared_ptr<Req>> fresh_;
-  // (m_) The names the last two cycles announced (routed ~sync requests aside) and how many of them
-  // fresh_ holds: a training step enqueues the same gradients every step, and once all of them are
-  // in the linger need not wait out its quiet time (loop()).
-  // (sorted name hashes, made by the enqueuing threads: admit() compares integers, and a collision
-  // only ends a linger early or late, never changes what runs)
-  std::vector<uint64_t> expect_;
+  ExpectSet expect_;  // (m_) the linger's expected set; fresh_ holds its hits
   bool adm_prof_ = false;     // (TIPS_NEG_TRACE) drain_locked's phases, per cycle in the trace
   int64_t adm_ns_[5] = {};
-  size_t expect_hits_ = 0;
   std::atomic<int64_t> last_arrival_ns_{0};  // (steady clock) the latest enqueue: the linger's clock
   NameMap by_name_;
   NameKey look_{0, std::string()};  // (m_) execute()'s lookup key
-  // the response cache (the negotiation thread's own: no lock)
-  static constexpr uint8_t kCachedOk = 2;  // a response entry: a cached name decided OK (then its id)
-  static constexpr size_t kCacheCap = 1 << 16;
-  struct CacheEntry {
-    std::string name;
-    int dtype;
-    int64_t count;
-    std::vector<int64_t> shape;
-    bool live;
-  };
-  struct IdState {  // (rank 0) this round's announces of a cached name
-    uint64_t mask = 0;   // the ranks that announced it by id
-    int n = 0;
-    bool table = false;  // a full record came: the rest of the round goes through the table
-  };
-  std::vector<CacheEntry> cache_;
-  std::unordered_map<NameKey, uint32_t, NameKeyHash> cache_ids_;
-  NameKey cache_look_{0, std::string()};
-  std::vector<IdState> idst_;
-  std::vector<uint32_t> id_ready_;
   std::atomic<int64_t> cached_decisions_{0};
-  int64_t decide_ns_ = 0;  // (rank 0, the trace) the last cycle's decide()
   HandleMap by_handle_;
   std::vector<std::string> log_;
   std::vector<hipEvent_t> ev_pool_;
@@ -1881,8 +1522,11 @@ bool route_collective(int type, int dtype, const int64_t* shape, int ndim, int r
     return false;
   }
   const std::string name = "~sync." + std::to_string((long long)n->sync_seq++);
-  const int64_t h = n->enqueue(name, nullptr, nullptr, shape, ndim, dtype, nullptr, type, root, nullptr, nullptr,
-                               nullptr, body);
+  ReqSpec q(name.c_str(), shape, ndim, dtype);
+  q.type = type;
+  q.root = root;
+  q.body = body;
+  const int64_t h = n->enqueue(q);
   if (h < 0) {
     *rc = (int)h;
     return true;
@@ -1954,6 +1598,14 @@ Negotiator* cached(bool create, int* code) {
   return tl.get();
 }
 
+// tips_poll, tips_wait, tips_on_done: the negotiation a handle belongs to, or null with the error set
+Negotiator* started() {
+  int code = 0;
+  Negotiator* n = cached(false, &code);
+  if (!n) fail(TIPS_ERR_NOT_INITIALIZED, "no named request was ever enqueued");
+  return n;
+}
+
 // The argument checks of a named request (before any negotiation state is touched)
 int check_named(const char* name, const void* in, void* out, const int64_t* shape, int ndim, int dtype, int type,
                 int root, tips_alloc_fn alloc) {
@@ -1978,7 +1630,13 @@ int64_t enqueue_named(const char* name, const void* in, void* out, const int64_t
   int code = TIPS_ERR_NOT_INITIALIZED;
   Negotiator* n = cached(true, &code);
   if (!n) return code;
-  return n->enqueue(name, in, out, shape, ndim, dtype, (hipStream_t)stream, type, root, alloc, actx, out_rows, nullptr);
+  ReqSpec q(name, shape, ndim, dtype, in, out, stream);
+  q.type = type;
+  q.root = root;
+  q.alloc = alloc;
+  q.actx = actx;
+  q.out_rows = out_rows;
+  return n->enqueue(q);
 }
 
 // tips_enqueue_allreduce[_shaped]_n: request i has shape dims(i) = {pointer, ndim}. Every request is
@@ -2007,9 +1665,10 @@ int enqueue_named_list(const char* const* names, const void* const* ins, void* c
             : d.second < 0 ? fail(TIPS_ERR_INVALID_ARG, "bad named allreduce request")
                            : check_named(names[i], ins[i], outs[i], d.first, d.second, dtype, TIPS_REQ_ALLREDUCE, 0, nullptr);
     if (e == 0 && !neg && !(neg = negotiator(&code))) e = code;
-    if (e == 0)
-      e = neg->prepare(ps[(size_t)i], names[i], ins[i], outs[i], d.first, d.second, dtype, (hipStream_t)stream,
-                       TIPS_REQ_ALLREDUCE, 0, nullptr, nullptr, nullptr, nullptr, &pr);
+    if (e == 0) {
+      ReqSpec q(names[i], d.first, d.second, dtype, ins[i], outs[i], stream);
+      e = neg->prepare(ps[(size_t)i], q, &pr);
+    }
     if (e) refused(i, e);
   }
   if (neg && env_i64("TIPS_LIST_ONE_LOCK", 1) == 0) {  // (A/B: one commit per request, as round 3)
@@ -2062,16 +1721,14 @@ int64_t tips_enqueue_allgather(const char* name, const void* in, const int64_t* 
 
 
 int tips_poll(int64_t handle) {
-  int code = 0;
-  Negotiator* n = cached(false, &code);
-  if (!n) return fail(TIPS_ERR_NOT_INITIALIZED, "no named request was ever enqueued");
+  Negotiator* n = started();
+  if (!n) return TIPS_ERR_NOT_INITIALIZED;
   return n->poll(handle, false);
 }
 
 int tips_wait(int64_t handle) {
-  int code = 0;
-  Negotiator* n = cached(false, &code);
-  if (!n) return fail(TIPS_ERR_NOT_INITIALIZED, "no named request was ever enqueued");
+  Negotiator* n = started();
+  if (!n) return TIPS_ERR_NOT_INITIALIZED;
   const int rc = n->poll(handle, true);
   return rc == 1 ? 0 : rc;
 }
@@ -2083,15 +1740,16 @@ int64_t tips_enqueue_allreduce_cb(const char* name, const void* in, void* out, c
   int code = TIPS_ERR_NOT_INITIALIZED;
   Negotiator* n = cached(true, &code);
   if (!n) return code;
-  return n->enqueue(name, in, out, shape, ndim, dtype, (hipStream_t)stream, TIPS_REQ_ALLREDUCE, 0, nullptr, nullptr,
-                    nullptr, nullptr, nullptr, fn, ctx);
+  ReqSpec q(name, shape, ndim, dtype, in, out, stream);
+  q.cb = fn;
+  q.cb_ctx = ctx;
+  return n->enqueue(q);
 }
 
 int tips_on_done(int64_t handle, tips_done_fn fn, void* ctx) {
   if (!fn) return fail(TIPS_ERR_INVALID_ARG, "null completion callback");
-  int code = 0;
-  Negotiator* n = cached(false, &code);
-  if (!n) return fail(TIPS_ERR_NOT_INITIALIZED, "no named request was ever enqueued");
+  Negotiator* n = started();
+  if (!n) return TIPS_ERR_NOT_INITIALIZED;
   return n->on_done(handle, fn, ctx);
 }
 
@@ -2273,15 +1931,16 @@ int tips_negotiation_selftest(int rank, int size, const char* host, int port, co
           q = q ? q + 1 : "";
         }
         if (shape.empty()) shape.push_back(cnt);
+        ReqSpec q(nm, shape.data(), (int)shape.size(), (int)dt);
+        q.type = type;
+        q.root = root;
         if (batching) {
           batch.emplace_back();
-          if (neg.prepare(batch.back(), nm, nullptr, nullptr, shape.data(), (int)shape.size(), (int)dt, nullptr, type,
-                          root, nullptr, nullptr, nullptr, nullptr, nullptr) != 0) {
+          if (neg.prepare(batch.back(), q) != 0) {
             rcs[k] = TIPS_ERR_INVALID_ARG;
             return;
           }
-        } else if (!issued_one(neg.enqueue(nm, nullptr, nullptr, shape.data(), (int)shape.size(), (int)dt, nullptr,
-                                           type, root))) {
+        } else if (!issued_one(neg.enqueue(q))) {
           return;
         }
       }
@@ -2338,8 +1997,10 @@ int tips_negotiation_stop_race_selftest(int threads, int per_thread, int stop_af
           for (int i = 0; i < per_thread; i++) {
             Slot& sl = slots[(size_t)t * per_thread + i];
             const std::string name = "r" + std::to_string(round) + "/t" + std::to_string(t) + "/" + std::to_string(i);
-            const int64_t h = neg.enqueue(name, nullptr, nullptr, shape, 1, TIPS_FLOAT32, nullptr, TIPS_REQ_ALLREDUCE, 0,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr, count_cb, &sl);
+            ReqSpec q(name.c_str(), shape, 1, TIPS_FLOAT32);
+            q.cb = count_cb;
+            q.cb_ctx = &sl;
+            const int64_t h = neg.enqueue(q);
             sl.accepted = h > 0;
           }
         });

@@ -26,6 +26,7 @@
 #else
 #include "../../include/tips_hip.h"
 #endif
+#include "err.h"
 #include "kernels.h"
 
 namespace tips {
@@ -36,10 +37,6 @@ constexpr int64_t kAlignBytes = 256;  // chunk / bucket-slot alignment (dwordx4 
 constexpr int64_t kPipelineMinChunk = (int64_t)16 << 20;
 // host-staging piece: 16 MiB sits at the top of the measured pipeline curve (profiles/r01_pcie_probe.jsonl)
 constexpr int64_t kHostPieceBytes = 16 << 20;
-
-// Records the calling thread's last error (tips_last_error) and returns `code`.
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-const std::string& last_error();
 
 #define HIP_TRY(expr)                                                                                  \
   do {                                                                                                 \
@@ -53,14 +50,6 @@ const std::string& last_error();
     if (r_ != ncclSuccess) return fail(TIPS_ERR_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r_)); \
   } while (0)
 
-#define TRY(expr)            \
-  do {                       \
-    int rc_ = (expr);        \
-    if (rc_ != 0) return rc_; \
-  } while (0)
-
-int64_t env_i64(const char* name, int64_t dflt);
-int env_first_int(const char* const* names, int dflt);
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int mod(int a, int p) { return ((a % p) + p) % p; }
 
@@ -336,7 +325,7 @@ void fusion_release(State& st);  // (shutdown)
 // one L3, and a pool it starts, or a mask computed on it, would inherit that.)
 const cpu_set_t& process_cpus();
 void pack_signals_release(State& st);  // fusion.cc: the merged pack's counters and signal words
-// control.cc: ConstructResponseMessage's rules over p request records (TIPS_REQUEST_WORDS each)
+// neg_protocol.cc: ConstructResponseMessage's rules over p request records (TIPS_REQUEST_WORDS each)
 int check_records(const int64_t* t, int p);
 // negotiate.cc: stop the negotiation thread (collective; call without holding st.mu)
 int negotiation_stop();
