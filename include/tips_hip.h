@@ -41,8 +41,10 @@ enum tips_dtype {
 };
 
 /* reduction codes = CollectiveOpKind (tips/core/collective/utils.h:21-25).
- * The reference only ever issues SUM (coordinator.cc:256-274); so does this
- * build: MAX/MIN return TIPS_ERR_UNSUPPORTED. */
+ * The reference only ever issues SUM (coordinator.cc:256-274), and tips_allreduce /
+ * tips_allreduce_checked keep answering MAX/MIN with TIPS_ERR_UNSUPPORTED. MAX and MIN are
+ * computed by the calls that take an op: tips_bucket_reduce, tips_multi_reduce and
+ * tips_allreduce_op (below, "MAX and MIN"). */
 enum tips_op {
   TIPS_OP_SUM = 0,
   TIPS_OP_MAX = 1,
@@ -183,6 +185,32 @@ TIPS_API int tips_multi_sum_scaled(void* dst, const void* const* srcs, int nsrc,
  * as an ALLREDUCE request, like tips_allreduce. Never captured or replayed as a graph (TIPS_GRAPHS). */
 TIPS_API int tips_allreduce_scaled(const void* in, void* out, int64_t count, int dtype, double prescale,
                                    double postscale, void* stream);
+
+/* ---- MAX and MIN: the calls that take the reduction op ---- */
+
+/* One definition for every call below (MAX and MIN). result[i] = the largest (TIPS_OP_MAX)
+ * or smallest (TIPS_OP_MIN) of the operands' element i, in the storage type, exact: nothing is rounded.
+ * INT32 / INT64 compare signed. FLOAT32 / FLOAT64 / FLOAT16 / BFLOAT16 follow IEEE 754-2019 maximum /
+ * minimum: if any operand is a NaN the result is a NaN (payload and quiet bit unspecified), -0 < +0
+ * (MAX(+0, -0) = +0, MIN(+0, -0) = -0), subnormals are kept, the infinities order as values. The
+ * result does not depend on the order of the operands, so every schedule returns the same bits. There
+ * is no scaled MAX / MIN. op outside {SUM, MAX, MIN} returns TIPS_ERR_INVALID_ARG; with TIPS_OP_SUM
+ * each call is its plain twin (tips_bucket_sum, tips_multi_sum, tips_allreduce), bit for bit. */
+
+/* dst[i] = op(a[i], b[i]): tips_bucket_sum's launch. In-place (dst == a or dst == b) allowed. */
+TIPS_API int tips_bucket_reduce(void* dst, const void* a, const void* b, int64_t count, int dtype, int op, void* stream);
+/* dst[i] = op over srcs[0..nsrc)[i], 1 <= nsrc <= 16 (one source: the copy): tips_multi_sum's launches. */
+TIPS_API int tips_multi_reduce(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, int op,
+                               void* stream);
+/* out = op over ranks of in: tips_allreduce (device pointers stream-ordered, or host pointers through
+ * the staged and the pipelined host paths; in == out allowed) under ring, direct and one-shot, chosen
+ * explicitly, by AUTO or by TUNE - the same plans, each sum replaced by the compare. At one rank: the
+ * copy. Under TIPS_ALGO_RCCL: ncclAllReduce with ncclMax / ncclMin, whose own treatment of NaNs and
+ * signed zeros applies. Under TIPS_ALGO_PEER MAX / MIN return TIPS_ERR_UNSUPPORTED on every rank, before
+ * any exchange. Routed through a running negotiation as an ALLREDUCE request, like
+ * tips_allreduce_scaled: the request record does not carry op, so op must be the same on every rank
+ * and is not validated. Never captured or replayed as a graph (TIPS_GRAPHS). */
+TIPS_API int tips_allreduce_op(const void* in, void* out, int64_t count, int dtype, int op, void* stream);
 
 /* ---- control plane: cross-rank request validation ---- */
 

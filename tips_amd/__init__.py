@@ -11,13 +11,15 @@ from .compression import Compression, Compressor, FP16Compressor, NoneCompressor
 from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadcast_async, allreduce_async_many, synchronize_many, allreduce_op, broadcast_op, poll, synchronize, broadcast_variables, bucket_sum, fused_allreduce,
                   fused_allreduce_, rank_op, registered_host_buffer, set_algorithm, set_consistency_check, size_op)
 from .ops import fused_allreduce_cast, fused_allreduce_flat, fused_allreduce_host, fused_allreduce_host_flat, fusion_stats
-from .ops import set_op_scaling
+from .ops import set_op_scaling, allreduce_reduce_op
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
 
 Average = 'Average'
 Sum = 'Sum'
+Min = 'Min'
+Max = 'Max'
 
 
 class IndexedSlices(object):
@@ -37,7 +39,7 @@ __all__ = [
     "is_initialized", "size", "rank", "size_op", "rank_op", "set_algorithm", "Compression", "Compressor",
     "NoneCompressor", "FP16Compressor", "Average", "Sum", "TipsBasics", "TipsError", "TipsLibraryError",
     "DistributedOptimizer", "DistributedGradientTape", "fused_allreduce_cast", "fused_allreduce_flat", "fused_allreduce_host", "fused_allreduce_host_flat", "fusion_stats",
-    "allreduce_scaled", "set_op_scaling",
+    "allreduce_scaled", "set_op_scaling", "Min", "Max", "allreduce_reduce_op",
 ]
 
 
@@ -94,7 +96,17 @@ def allreduce(tensor,
     divided by size() for op=Average, as the reference does there. A torch
     sparse COO tensor gets the same treatment on its nonzeros. The result
     represents the summed tensor.
+
+    op=Max / op=Min return the elementwise maximum / minimum over the ranks
+    (ops.allreduce_reduce_op -> tips_allreduce_op), whatever set_op_scaling
+    says: exact in the tensor's dtype, integers compared signed, floats by
+    IEEE 754-2019 maximum / minimum (a NaN on any rank gives a NaN, -0 < +0).
+    `compression` composes as for the sum. They raise ValueError with a scale
+    factor other than 1, a sparse input or a `name` (named requests carry SUM
+    only).
     """
+    if op in (Max, Min):
+        return _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name)
     if isinstance(tensor, IndexedSlices):
         values = allgather_op(tensor.values)
         indices = allgather_op(tensor.indices)
@@ -117,6 +129,27 @@ def allreduce(tensor,
     else:
         summed_tensor_compressed = allreduce_op(tensor_compressed, name=name)
     return compression.decompress(summed_tensor_compressed, ctx)
+
+
+def _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name):
+    """allreduce(op=Max | Min): the argument checks (before anything is initialised), then compress,
+    reduce, decompress."""
+    if float(prescale_factor) != 1.0 or float(postscale_factor) != 1.0:
+        raise ValueError("op=%s takes no prescale_factor / postscale_factor: scaling does not combine with a "
+                         "maximum or minimum" % op)
+    if isinstance(tensor, IndexedSlices) or (_tensors.is_torch(tensor) and tensor.is_sparse):
+        raise ValueError("op=%s is not defined for sparse inputs (their allgather branch sums repeated indices): "
+                         "densify first" % op)
+    if name is not None:
+        raise ValueError("op=%s takes no name: named requests go through the negotiation, which carries SUM only" % op)
+    tensor_compressed, ctx = compression.compress(tensor)
+    return compression.decompress(allreduce_reduce_op(tensor_compressed, op), ctx)
+
+
+def _no_minmax_grads(op):
+    if op in (Max, Min):
+        raise ValueError("op=%s is not supported for gradient lists: the fused reductions carry SUM only "
+                         "(reduce single tensors with allreduce(tensor, op=%s))" % (op, op))
 
 
 def _allreduce_cond(tensor, *args, **kwargs):
@@ -164,6 +197,7 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     each. gradient_predivide_factor f (op=Average only) splits the division:
     prescale 1/f before the sums, postscale f/size() after them.
     """
+    _no_minmax_grads(op)
     if sparse_as_dense:
         grads = [_to_dense(g) if g is not None else g for g in grads]
     if size() <= 1:
@@ -189,6 +223,7 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
         pipelined H2D -> allreduce -> D2H straight into one page-locked flat host buffer, the
         outputs views of it (reused as the device flat outputs are);
       - the rest (sparse) one by one, through the reference's allgather branch."""
+    _no_minmax_grads(op)
     none = compression is Compression.none
     global _DATA_PTR
     if _DATA_PTR is None:

@@ -88,6 +88,12 @@ _SIGNATURES = [
     ("tips_allreduce_scaled", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
       ctypes.c_void_p]),
+    ("tips_bucket_reduce", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    ("tips_multi_reduce", ctypes.c_int,
+     [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    ("tips_allreduce_op", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

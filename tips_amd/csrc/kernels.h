@@ -22,15 +22,28 @@ hipError_t launch_multi_sum(void* dst, const void* const* srcs, int nsrc, int64_
 // (256 lanes, 16 KiB per source per workgroup, no occupancy cap). Same bits as launch_multi_sum.
 hipError_t launch_multi_sum_remote(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, hipStream_t s);
 
+// MAX / MIN (DESIGN.md §MAX and MIN): the same launches with the add replaced by an exact compare in
+// the storage type - signed for the integers, IEEE 754-2019 maximum / minimum for the floats (a NaN
+// operand gives a NaN, -0 < +0, subnormals kept). op: the C-ABI's tips_op values; kOpSum forwards to
+// launch_sum2 / launch_multi_sum. One source is the copy, as in launch_multi_sum.
+enum { kOpSum = 0, kOpMax = 1, kOpMin = 2 };
+hipError_t launch_reduce2(void* dst, const void* a, const void* b, int64_t n, int dtype, int op, hipStream_t s);
+hipError_t launch_multi_reduce(void* dst, const void* const* srcs, int nsrc, int64_t n, int dtype, int op, hipStream_t s);
+
 // Scaled forms (float dtypes; DESIGN.md §Scaled allreduce): result = post * SUM (pre * x), in the
 // working type (fp32 for f32 / f16 / bf16, f64 for f64), every multiply and add a separate IEEE
 // operation, one rounding at the store. Bit j of `raw` marks source j as a rank's raw input, to be
 // multiplied by pre where it is read; the other sources are partial sums that already carry it. The
 // launch shapes are those of launch_sum2 / launch_multi_sum / launch_copy_buf; with nothing to scale
 // (pre == 1 or no raw source, and post == 1) they are those launchers.
+// The struct also carries the call's reduction op down the schedules (kOpSum unless the call is
+// tips_allreduce_op's MAX / MIN, which never comes with factors).
 struct Scale {
   double pre = 1.0, post = 1.0;
+  int op = kOpSum;
   bool on() const { return pre != 1.0 || post != 1.0; }
+  bool minmax() const { return op != kOpSum; }
+  bool plain() const { return !on() && !minmax(); }  // the unscaled SUM: what a graph may capture
 };
 hipError_t launch_sum2_scaled(void* dst, const void* a, const void* b, int64_t n, int dtype, double pre, double post,
                               unsigned raw, hipStream_t s);

@@ -314,6 +314,110 @@ __device__ __forceinline__ u32x4 fold_store(typename Wide<DT>::A acc, ScaleArgs<
   return scaled_store<DT>(acc, sc.post);
 }
 
+// ---------------------------------------------------------------------------
+// MAX / MIN forms (DESIGN.md §MAX and MIN): result = the largest (smallest) of the operands, in the
+// storage type, exact. The sum, fold and scalar kernels take one MinMaxArgs<DT, IS_MAX> in the place of
+// a ScaleArgs<DT>: an empty tag, the op a template parameter, so each op's compare is one instruction
+// (v_maximum3_f32 / v_pk_maximum3_f16 / v_max_i32 ...) and not a select between two. Floats follow
+// IEEE 754-2019 maximum / minimum: a NaN operand gives a NaN, -0 < +0, subnormals are kept
+// (__builtin_elementwise_maximum; __builtin_elementwise_max would drop the NaN). Integers compare
+// signed - the sums' unsigned vectors are cast first. bf16 compares as f32 after the << 16 and keeps the
+// winner's upper half (nothing to round); the fold widens f16 to fp32 like the sum's fold, which is
+// exact for a compare, the 2-input form compares packed halves. No operand order can change a bit
+// of the result (a NaN's payload excepted), so every schedule returns the same bits.
+template <int DT, bool IS_MAX>
+struct MinMaxArgs {};
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef long long i64x2 __attribute__((ext_vector_type(2)));
+
+template <bool IS_MAX, class V>
+__device__ __forceinline__ V pick_float(V a, V b) {
+  if constexpr (IS_MAX) return __builtin_elementwise_maximum(a, b);
+  else return __builtin_elementwise_minimum(a, b);
+}
+template <bool IS_MAX, class V>
+__device__ __forceinline__ V pick_int(V a, V b) {
+  if constexpr (IS_MAX) return __builtin_elementwise_max(a, b);
+  else return __builtin_elementwise_min(a, b);
+}
+
+// the compare in the fold's accumulator type Wide<DT>::A (unsigned vectors for the integers)
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ typename Wide<DT>::A pick_wide(typename Wide<DT>::A a, typename Wide<DT>::A b) {
+  if constexpr (DT == kI32) return __builtin_bit_cast(u32x4, pick_int<IS_MAX>(__builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, b)));
+  else if constexpr (DT == kI64) return __builtin_bit_cast(u64x2, pick_int<IS_MAX>(__builtin_bit_cast(i64x2, a), __builtin_bit_cast(i64x2, b)));
+  else return pick_float<IS_MAX>(a, b);
+}
+
+// two bf16 halves' winners (f32 values whose low 16 bits are zero) back into one word per pair
+__device__ __forceinline__ u32x4 bf16_pack_exact(f32x4 lo, f32x4 hi) {
+  return (__builtin_bit_cast(u32x4, lo) >> 16u) | (__builtin_bit_cast(u32x4, hi) & 0xffff0000u);
+}
+
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ u32x4 sum16(u32x4 a, u32x4 b, MinMaxArgs<DT, IS_MAX>) {
+  if constexpr (DT == kF16) {
+    return __builtin_bit_cast(u32x4, pick_float<IS_MAX>(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b)));
+  } else if constexpr (DT == kBF16) {
+    return bf16_pack_exact(pick_float<IS_MAX>(bf16_lo(a), bf16_lo(b)), pick_float<IS_MAX>(bf16_hi(a), bf16_hi(b)));
+  } else {
+    return Wide<DT>::store(pick_wide<DT, IS_MAX>(Wide<DT>::load(a), Wide<DT>::load(b)));
+  }
+}
+
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ typename Wide<DT>::A fold_first(u32x4 v, MinMaxArgs<DT, IS_MAX>) {
+  return Wide<DT>::load(v);
+}
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ typename Wide<DT>::A fold_next(typename Wide<DT>::A acc, u32x4 v, int, MinMaxArgs<DT, IS_MAX>) {
+  return pick_wide<DT, IS_MAX>(acc, Wide<DT>::load(v));
+}
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ u32x4 fold_store(typename Wide<DT>::A acc, MinMaxArgs<DT, IS_MAX>) {
+  if constexpr (DT == kBF16) {
+    return bf16_pack_exact(f32x4{acc[0], acc[1], acc[2], acc[3]}, f32x4{acc[4], acc[5], acc[6], acc[7]});
+  } else {
+    return Wide<DT>::store(acc);  // (f16: every winner is a half's value, the conversion rounds nothing)
+  }
+}
+
+// one element (tails and the unaligned fallback): the same compares, signed for the integers
+template <int DT>
+struct CmpOf {
+  using T = typename ScalarOf<DT>::T;
+};
+template <>
+struct CmpOf<kI32> {
+  using T = int;
+};
+template <>
+struct CmpOf<kI64> {
+  using T = long long;
+};
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ void fold_elem(void* dst, const void* const* srcs, int nsrc, int64_t i, MinMaxArgs<DT, IS_MAX>) {
+  if constexpr (DT == kBF16) {
+    float acc = load_work<kBF16>(srcs[0], i);
+    for (int j = 1; j < nsrc; j++) acc = pick_float<IS_MAX>(acc, load_work<kBF16>(srcs[j], i));
+    ((unsigned short*)dst)[i] = (unsigned short)(__builtin_bit_cast(unsigned, acc) >> 16);
+  } else {
+    using T = typename CmpOf<DT>::T;
+    T acc = ((const T*)srcs[0])[i];
+    for (int j = 1; j < nsrc; j++) {
+      if constexpr (DT == kI32 || DT == kI64) acc = pick_int<IS_MAX>(acc, ((const T*)srcs[j])[i]);
+      else acc = pick_float<IS_MAX>(acc, ((const T*)srcs[j])[i]);
+    }
+    ((T*)dst)[i] = acc;
+  }
+}
+template <int DT, bool IS_MAX>
+__device__ __forceinline__ void sum_elem(void* dst, const void* a, const void* b, int64_t i, MinMaxArgs<DT, IS_MAX> mm) {
+  const void* s[2] = {a, b};
+  fold_elem<DT>(dst, s, 2, i, mm);
+}
+
 // the contiguous copy's vector and trailing bytes: plain, or scaled (source 0 is raw)
 __device__ __forceinline__ u32x4 copy16(u32x4 v) { return v; }
 template <int DT>
@@ -363,7 +467,8 @@ __device__ __forceinline__ int64_t stripe_tile(unsigned b, unsigned grid, int64_
 // 512 KiB stripes (round 6; rounds 2-5: 256 lanes with sc1 stores, which won when one buffer
 // triple was re-read, 7.46 vs 7.10 TB/s, profiles/r01_sum_sweep_f.jsonl). Each workgroup's
 // descriptors cover exactly its tile, so the hardware range check drops lanes past the end.
-// SC: empty (the plain sum), or one ScaleArgs<DT> (the scaled sum, see "Scaled forms" above).
+// SC: empty (the plain sum), one ScaleArgs<DT> (the scaled sum, see "Scaled forms" above), or one
+// MinMaxArgs<DT, IS_MAX> (MAX / MIN, see "MAX / MIN forms").
 template <int DT, int LAUX, int SAUX, int U = 1, int BLOCK = 256, class... SC>
 __global__ __launch_bounds__(BLOCK) void sum2_buf_kernel(u32x4* __restrict__ dst, const u32x4* __restrict__ a,
                                                         const u32x4* __restrict__ b, int64_t nvec,
@@ -425,7 +530,7 @@ struct SrcList {
 // Buffer-op form of the multi-input sum: one descriptor per source covering
 // this workgroup's tile, cache-policy bits on the loads (LAUX) and sc1 stores,
 // every source's vectors in flight before the fold (as sum2_buf_kernel).
-// SC: empty (the plain fold), or one ScaleArgs<DT> (the scaled fold).
+// SC: empty (the plain fold), one ScaleArgs<DT> (the scaled fold), or one MinMaxArgs<DT, IS_MAX>.
 template <int DT, int NSRC, int U, int LAUX, int BLOCK = kBlock, int SAUX = 16, class... SC>
 __global__ __launch_bounds__(BLOCK) void multi_sum_buf_kernel(u32x4* __restrict__ dst, SrcList srcs, int64_t nvec,
                                                              int64_t tail_begin, int64_t n, int64_t stripe, SC... sc) {

@@ -267,7 +267,9 @@ void rccl_env_defaults();  // before any ncclCommInitRank of ours
 
 // schedules.cc: device-resident allreduce, caller holds st.mu. With a scale (sc.on(); float dtypes):
 // out = post * SUM over ranks of (pre * in), the factors applied inside the schedule's sum kernels
-// (unfused under TIPS_ALGO_RCCL / TIPS_ALGO_PEER); never captured or replayed as a graph.
+// (unfused under TIPS_ALGO_RCCL / TIPS_ALGO_PEER); never captured or replayed as a graph. With sc.op
+// MAX or MIN (sc.minmax(), never with factors): the same schedules with the compare in place of the
+// sum (ncclMax / ncclMin under TIPS_ALGO_RCCL, TIPS_ERR_UNSUPPORTED under TIPS_ALGO_PEER), never a graph.
 int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype, hipStream_t stream,
                      const tips::Scale& sc = tips::Scale());
 // the checks every scaled entry point makes on its factors: TIPS_ERR_INVALID_ARG for a non-finite

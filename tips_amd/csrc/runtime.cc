@@ -263,7 +263,7 @@ int tips_xfer(void* const* dsts, const void* const* srcs, const int64_t* bytes, 
 }
 #endif  // TIPS_DEV
 
-// tips_allreduce and tips_allreduce_scaled (sc.on()): one body, so both take the same route - through
+// tips_allreduce, tips_allreduce_scaled (sc.on()) and tips_allreduce_op (sc.op): one body, so all take the same route - through
 // a running negotiation as an ALLREDUCE request, the pipelined pieces for large host buffers, the
 // staged path for small ones.
 static int allreduce_entry(const void* in, void* out, int64_t count, int dtype, void* stream, const tips::Scale& sc) {
@@ -300,6 +300,47 @@ int tips_allreduce_scaled(const void* in, void* out, int64_t count, int dtype, d
   TRY(check_scale(dtype, prescale, postscale));
   if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
   return allreduce_entry(in, out, count, dtype, stream, tips::Scale{prescale, postscale});
+}
+
+// ---- the calls that take the reduction op (SUM: each is its plain twin) ----
+
+static_assert((int)TIPS_OP_SUM == tips::kOpSum && (int)TIPS_OP_MAX == tips::kOpMax && (int)TIPS_OP_MIN == tips::kOpMin,
+              "the launchers take the C-ABI's op codes");
+
+static int check_op(int op) {
+  if (op != TIPS_OP_SUM && op != TIPS_OP_MAX && op != TIPS_OP_MIN)
+    return fail(TIPS_ERR_INVALID_ARG, "bad reduction op %d (SUM, MAX or MIN)", op);
+  return 0;
+}
+
+int tips_bucket_reduce(void* dst, const void* a, const void* b, int64_t count, int dtype, int op, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_op(op));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  if (!dst || !a || !b) return fail(TIPS_ERR_INVALID_ARG, "null pointer");
+  HIP_TRY(tips::launch_reduce2(dst, a, b, count, dtype, op, (hipStream_t)stream));
+  return 0;
+}
+
+int tips_multi_reduce(void* dst, const void* const* srcs, int nsrc, int64_t count, int dtype, int op, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_op(op));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  if (count == 0) return 0;
+  if (!dst || !srcs) return fail(TIPS_ERR_INVALID_ARG, "null pointer");
+  if (nsrc < 1 || nsrc > tips::kMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1..%d", tips::kMaxSrcs);
+  HIP_TRY(tips::launch_multi_reduce(dst, srcs, nsrc, count, dtype, op, (hipStream_t)stream));
+  return 0;
+}
+
+int tips_allreduce_op(const void* in, void* out, int64_t count, int dtype, int op, void* stream) {
+  TRY(check_dtype(dtype));
+  TRY(check_op(op));
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  tips::Scale sc;
+  sc.op = op;
+  return allreduce_entry(in, out, count, dtype, stream, sc);
 }
 
 int tips_scale(void* dst, const void* src, int64_t count, int dtype, double factor, void* stream) {

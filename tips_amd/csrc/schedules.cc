@@ -24,18 +24,22 @@ namespace {
 
 // A scaled allreduce (sc.on()) multiplies the sum's raw sources by pre and, when the sum completes
 // its elements, the result by post - inside the same launch (kernels_device.h, scaled forms).
+// A MAX / MIN call (sc.minmax()) runs the same plan with every sum replaced by the compare: the plans
+// say which bytes meet where, not what is done with them.
 int launch_psum(const PSum& s, char* const* base, int dtype, hipStream_t stream, const tips::Scale& sc = tips::Scale()) {
   void* dst = base[s.dst.buf] + s.dst.off;
   const double post = s.last ? sc.post : 1.0;
   if (s.nsrc == 2) {
     const void *a = base[s.src[0].buf] + s.src[0].off, *b = base[s.src[1].buf] + s.src[1].off;
-    if (sc.on()) HIP_TRY(tips::launch_sum2_scaled(dst, a, b, s.count, dtype, sc.pre, post, s.raw, stream));
+    if (sc.minmax()) HIP_TRY(tips::launch_reduce2(dst, a, b, s.count, dtype, sc.op, stream));
+    else if (sc.on()) HIP_TRY(tips::launch_sum2_scaled(dst, a, b, s.count, dtype, sc.pre, post, s.raw, stream));
     else HIP_TRY(tips::launch_sum2(dst, a, b, s.count, dtype, stream));
     return 0;
   }
   const void* srcs[tips::kMaxSrcs];
   for (int j = 0; j < s.nsrc; j++) srcs[j] = base[s.src[j].buf] + s.src[j].off;
-  if (sc.on()) HIP_TRY(tips::launch_multi_sum_scaled(dst, srcs, s.nsrc, s.count, dtype, sc.pre, post, s.raw, stream));
+  if (sc.minmax()) HIP_TRY(tips::launch_multi_reduce(dst, srcs, s.nsrc, s.count, dtype, sc.op, stream));
+  else if (sc.on()) HIP_TRY(tips::launch_multi_sum_scaled(dst, srcs, s.nsrc, s.count, dtype, sc.pre, post, s.raw, stream));
   else HIP_TRY(tips::launch_multi_sum(dst, srcs, s.nsrc, s.count, dtype, stream));
   return 0;
 }
@@ -416,7 +420,8 @@ int grow_staging(State& st, int64_t bytes) {
   return 0;
 }
 
-// A scaled call (sc.on()) is never captured or replayed: a graph would freeze its factors.
+// A scaled call (sc.on()) is never captured or replayed: a graph would freeze its factors. Nor is a
+// MAX / MIN call (sc.minmax()): the graph keys do not carry the op.
 int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t user, int L = 1,
              const tips::Scale& sc = tips::Scale()) {
   L = std::max(1, std::min(L, (int)pl.steps.size()));
@@ -430,7 +435,7 @@ int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t u
   TRY(st.recv_ev.ensure(nsteps));
   TRY(st.sum_ev.ensure(nsteps));
   char* base[3] = {(char*)in, out, (char*)st.staging.p};
-  const bool eligible = L == 1 && !sc.on() && graph_eligible(st, pl, user);
+  const bool eligible = L == 1 && sc.plain() && graph_eligible(st, pl, user);
   bool key_new = false;
   if (eligible) {
     hipGraphExec_t exec = plan_graph(st, pl, base, false, &key_new);
@@ -441,7 +446,7 @@ int run_plan(State& st, const Plan& pl, const char* in, char* out, hipStream_t u
   TRY(prologue(st, user, L));
   // this call's host wait may just have widened the replay limit (replays_mixed): its key counts as
   // seen, so its next call is captured instead of waiting once more
-  if (L == 1 && !eligible && !sc.on() && graph_eligible(st, pl, user)) (void)plan_graph(st, pl, base, true, &key_new);
+  if (L == 1 && !eligible && sc.plain() && graph_eligible(st, pl, user)) (void)plan_graph(st, pl, base, true, &key_new);
   // A bucket that waits for a replay at an address never seen before cannot become a replay by
   // its next call. One shape doing that again and again (a buffer reallocated at a new address every
   // step) would wait on every call, and each wait stalls the host until the device has run the
@@ -474,6 +479,12 @@ int size_class(int64_t bytes) {
   return c;  // ceil(log2(bytes))
 }
 
+// The peer schedule's push and pull-fold sum only: a MAX / MIN call is refused before any exchange or
+// barrier (every rank takes this branch: op is the same on all of them).
+int peer_no_minmax() {
+  return fail(TIPS_ERR_UNSUPPORTED, "TIPS_ALGO_PEER reduces with SUM only: MAX / MIN need ring, direct, oneshot or rccl");
+}
+
 // The peer schedule and ncclAllReduce do their own sums: a scaled call wraps them unfused - a scaled
 // copy of in into out (pre), the plain allreduce in place on out, a scale of out (post).
 template <class F>
@@ -487,6 +498,7 @@ int scaled_around(const void* in, void* out, int64_t n, int dtype, hipStream_t s
 int run_choice(State& st, const Choice& c, const char* in, char* out, int64_t n, int dtype, hipStream_t s,
                const tips::Scale& sc = tips::Scale()) {
   if (c.algo == TIPS_ALGO_PEER) {
+    if (sc.minmax()) return peer_no_minmax();
     if (sc.on()) return scaled_around(in, out, n, dtype, s, sc, [&] { return peer_allreduce(st, out, out, n, dtype, s); });
     return peer_allreduce(st, in, out, n, dtype, s);
   }
@@ -634,7 +646,8 @@ int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype,
     TRY(ensure_comm(st));
     if (sc.on()) HIP_TRY(tips::launch_scale_buf(out, in, n, dtype, sc.pre, 1.0, stream));  // (unfused, as scaled_around)
     TRY(rccl_enter(st, stream));
-    NCCL_TRY(ncclAllReduce(sc.on() ? out : in, out, (size_t)n, nccl_type(dtype), ncclSum, st.comm, stream));
+    const ncclRedOp_t red = sc.op == tips::kOpMax ? ncclMax : sc.op == tips::kOpMin ? ncclMin : ncclSum;
+    NCCL_TRY(ncclAllReduce(sc.on() ? out : in, out, (size_t)n, nccl_type(dtype), red, st.comm, stream));
     TRY(rccl_leave(st, stream));
     if (sc.on()) HIP_TRY(tips::launch_scale_buf(out, out, n, dtype, 1.0, sc.post, stream));
     return 0;
@@ -645,6 +658,7 @@ int allreduce_device(State& st, const void* in, void* out, int64_t n, int dtype,
     return 0;
   }
   if (algo == TIPS_ALGO_PEER && st.size <= tips::kMaxSrcs) {
+    if (sc.minmax()) return peer_no_minmax();
     if (sc.on())
       return scaled_around(in, out, n, dtype, stream, sc,
                            [&] { return peer_allreduce(st, (const char*)out, (char*)out, n, dtype, stream); });

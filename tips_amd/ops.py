@@ -107,6 +107,32 @@ def allreduce_scaled_op(tensor, prescale_factor=1.0, postscale_factor=1.0, name=
     return out
 
 
+_REDUCE_OPS = {"Sum": _lib.OP_SUM, "Max": _lib.OP_MAX, "Min": _lib.OP_MIN}
+
+
+def allreduce_reduce_op(tensor, op, name=None):
+    """`op` ('Sum', 'Max' or 'Min') of `tensor` over all ranks, out of place (tips_allreduce_op):
+    Max / Min are exact in the tensor's dtype - integers compared signed, floats by IEEE 754-2019
+    maximum / minimum (a NaN on any rank gives a NaN, -0 < +0, subnormals kept) - and independent of
+    the schedule; 'Sum' is allreduce_op's sum. Device or host tensors, as allreduce_op; `op` must be
+    the same on every rank. A `name` is refused for Max / Min: named requests carry SUM only."""
+    if op not in _REDUCE_OPS:
+        raise ValueError("allreduce_reduce_op: op must be one of %s (got %r)" % (sorted(_REDUCE_OPS), op))
+    if name is not None:
+        if op != "Sum":
+            raise ValueError("op=%s takes no name: named requests go through the negotiation, which carries SUM only" % op)
+        return allreduce_op(tensor, name=name)
+    basics.init()
+    code = tensors.dtype_code(tensor)
+    src = tensors.contiguous(tensor)
+    out = _HOST_OUT.take(src) if not tensors.is_device(src) else tensors.empty_like(src)
+    n = tensors.numel(src)
+    if n:
+        _lib.call("tips_allreduce_op", tensors.data_ptr(src), tensors.data_ptr(out), n, code, _REDUCE_OPS[op],
+                  tensors.stream_of(src))
+    return out
+
+
 def allreduce_op(tensor, name=None):
     """Sum `tensor` over all ranks (ops.py:61-65 -> MPIAllreduce, ops.cc:86-115). With a `name`,
     through the negotiation like the reference's op (rank 0 validates and orders it; the name

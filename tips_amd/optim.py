@@ -557,6 +557,9 @@ class _DistributedOptimizer(object):
 def _validate(op, gradient_predivide_factor, num_groups, groups):
     """The argument checks DistributedOptimizer and DistributedGradientTape share
     (__init__.py:408-423, 540-556), with the reference's messages; returns `groups`."""
+    if op in ('Max', 'Min'):
+        raise ValueError('op=%s is not supported for gradients: the fused gradient reductions carry SUM only '
+                         '(reduce single tensors with allreduce(tensor, op=%s))' % (op, op))
     if gradient_predivide_factor != 1.0:
         if op != Average:
             raise ValueError('gradient_predivide_factor not supported with op != Average')
