@@ -212,6 +212,55 @@ TIPS_API int tips_multi_reduce(void* dst, const void* const* srcs, int nsrc, int
  * and is not validated. Never captured or replayed as a graph (TIPS_GRAPHS). */
 TIPS_API int tips_allreduce_op(const void* in, void* out, int64_t count, int dtype, int op, void* stream);
 
+/* ---- sparse gradients: ordered row sums (Sparse allreduce) ---- */
+
+/* One definition for the calls below. Inputs: values[n][row_elems] of one dtype, indices[n] (int64)
+ * and a dense row count `rows`. Result: dense[rows][row_elems] with
+ *     dense[j][:] = postscale * (e(x1) + e(x2) + ... + e(xk)),   e(x) = prescale * x
+ * where x1 ... xk are the rows values[i][:] with indices[i] == j in ascending position i (for the
+ * collective: ascending (rank, position)), folded left to right starting from the first row itself
+ * (a lone -0 stays -0); a row no entry names is +0. The arithmetic runs in the working type - fp32
+ * for FLOAT32 / FLOAT16 / BFLOAT16, f64 for FLOAT64, the integer type itself for INT32 / INT64 -
+ * every multiply and add a separate IEEE operation, one rounding to the storage type at the store;
+ * with both factors 1 there is no multiply at all. An integer dtype with a factor other than 1
+ * returns TIPS_ERR_UNSUPPORTED, a factor that is not finite TIPS_ERR_INVALID_ARG; there is no MAX /
+ * MIN form. An entry whose index is outside [0, rows) is skipped - it never reaches an address
+ * computation - and counted (tips_sparse_stats). The result depends on nothing but the inputs: two
+ * runs give the same bits, and so do one rank holding all the entries and p ranks holding them split
+ * in rank order. Every pointer is a device pointer: a host pointer returns TIPS_ERR_UNSUPPORTED with
+ * a message and is not staged. (The reference's tf.IndexedSlices branch, tips/tensorflow/
+ * __init__.py:59-74, allgathers and leaves the sums to the consumer.) */
+
+/* Bytes of workspace tips_rows_sum needs for `rows` dense rows and `n` entries:
+ * 8 * (2 * rows + 2) + 16 * n (counts / offsets, cursors, placed and ordered entry ids). < 0 = error. */
+TIPS_API int64_t tips_rows_sum_workspace(int64_t rows, int64_t n);
+/* The local operation: dst[rows][row_elems] from this process's values / indices. Stream-ordered,
+ * needs no tips_init (like tips_bucket_sum). Every row of dst is written exactly once (n == 0 writes
+ * zeros); rows == 0 or row_elems == 0 is TIPS_OK with nothing launched. Negative sizes and a
+ * workspace smaller than tips_rows_sum_workspace(rows, n) (or not 8-B aligned) return
+ * TIPS_ERR_INVALID_ARG. dst, values, indices and workspace must not overlap. When every entry names
+ * one row, ordering that row's entries costs O(n^2 / lanes of the device). */
+TIPS_API int tips_rows_sum(void* dst, int64_t rows, int64_t row_elems, const void* values, const int64_t* indices,
+                           int64_t n, int dtype, double prescale, double postscale, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+/* The collective: dense_out[rows][row_elems] = the row sum over every rank's entries, the same on
+ * every rank. The ranks first exchange {n, rows, row_elems, dtype} on the host (the gather behind
+ * tips_allgather_i64): a difference in rows, row_elems or dtype returns TIPS_ERR_MISMATCH on every
+ * rank before any device exchange. Indices and values then go through tips_allgatherv's path into
+ * runtime scratch (ranks with n == 0 take part), and the row sum runs on the gathered arrays; at one
+ * rank it runs straight on the caller's arrays, no copy. n may differ per rank; the factors must be
+ * the same on every rank (not validated). Stream-ordered. Never captured or replayed as a graph.
+ * While a negotiation runs (after the first named request) it returns TIPS_ERR_UNSUPPORTED: named
+ * sparse requests are not implemented. */
+TIPS_API int tips_sparse_allreduce(const void* values, const int64_t* indices, int64_t n, int64_t rows,
+                                   int64_t row_elems, int dtype, double prescale, double postscale, void* dense_out,
+                                   void* stream);
+/* Counters of this process since the library was loaded: row sums launched (by either call above),
+ * the entries they covered, and the entries skipped for an index outside [0, rows) - read back from
+ * the device counter, so THIS CALL SYNCHRONISES THE DEVICE. Any pointer may be NULL (with
+ * bad_indices NULL nothing is synchronised). */
+TIPS_API int tips_sparse_stats(int64_t* calls, int64_t* entries, int64_t* bad_indices);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

@@ -6,6 +6,8 @@ compression.py), over numpy arrays and torch tensors instead of TF tensors
 (TensorFlow is not in this image). Everything below reaches the GPU through
 libtips_hip.so (include/tips_hip.h); there is no CPU fallback.
 """
+import os as _os
+
 from .basics import TipsBasics, init, is_initialized, rank, shutdown, size
 from .compression import Compression, Compressor, FP16Compressor, NoneCompressor
 from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadcast_async, allreduce_async_many, synchronize_many, allreduce_op, broadcast_op, poll, synchronize, broadcast_variables, bucket_sum, fused_allreduce,
@@ -40,6 +42,7 @@ __all__ = [
     "NoneCompressor", "FP16Compressor", "Average", "Sum", "TipsBasics", "TipsError", "TipsLibraryError",
     "DistributedOptimizer", "DistributedGradientTape", "fused_allreduce_cast", "fused_allreduce_flat", "fused_allreduce_host", "fused_allreduce_host_flat", "fusion_stats",
     "allreduce_scaled", "set_op_scaling", "Min", "Max", "allreduce_reduce_op",
+    "sparse_allreduce", "set_sparse_reduce", "sparse_stats",
 ]
 
 
@@ -146,6 +149,121 @@ def _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor
     return compression.decompress(allreduce_reduce_op(tensor_compressed, op), ctx)
 
 
+_sparse_reduce = _os.environ.get("TIPS_SPARSE_REDUCE", "0") == "1"
+
+
+def set_sparse_reduce(enabled):
+    """Whether allreduce_grads(..., sparse_as_dense=True), DistributedOptimizer and
+    DistributedGradientTape send device sparse gradients through sparse_allreduce (TIPS_SPARSE_REDUCE=1
+    sets the initial value). Off, the default, is today's route: torch.index_add_ builds the dense
+    table on every rank and the whole table is allreduced. On, only the entries cross the links and
+    the ordered row-sum kernels build the table - the same on every rank and from run to run. Host
+    sparse gradients, and any list reduced with a compression, keep today's route. The setting must be
+    the same on every rank."""
+    global _sparse_reduce
+    _sparse_reduce = bool(enabled)
+
+
+def _sparse_parts(slices, scaled):
+    """(values [n, ...] contiguous, indices [n] int64, dense_shape) of an IndexedSlices or a torch
+    sparse COO tensor, on one device; ValueError for what sparse_allreduce does not take (`scaled`:
+    the call carries a factor or op=Average, which integer values refuse)."""
+    if isinstance(slices, IndexedSlices):
+        if slices.dense_shape is None:
+            raise ValueError("sparse_allreduce needs the IndexedSlices' dense_shape")
+        values, indices = slices.values, slices.indices
+        shape = tuple(int(d) for d in slices.dense_shape)
+    elif _tensors.is_torch(slices) and slices.is_sparse:
+        if slices.sparse_dim() != 1:
+            raise ValueError("sparse_allreduce takes a COO tensor with one sparse dimension (the row index) and dense "
+                             "trailing dimensions; this one has %d sparse dimensions" % slices.sparse_dim())
+        values, indices = slices._values(), slices._indices()[0]
+        shape = tuple(int(d) for d in slices.shape)
+    else:
+        raise ValueError("sparse_allreduce takes an IndexedSlices or a torch sparse COO tensor (got %s)" % type(slices).__name__)
+    if scaled and _ops._is_integer(values):
+        raise ValueError("integer values (dtype %s) take no scale factor and no op=Average: reduce with op=Sum"
+                         % values.dtype)
+    if not (_tensors.is_device(values) and _tensors.is_device(indices)):
+        raise ValueError("sparse_allreduce takes device tensors only (host pointers are not staged): host sparse "
+                         "gradients go through the allgather branch, allreduce(IndexedSlices)")
+    if values.device != indices.device:
+        raise ValueError("values and indices must be on one device")
+    import torch
+    if indices.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise ValueError("indices must be integers (got %s)" % indices.dtype)
+    if len(shape) < 1 or indices.dim() != 1 or values.dim() < 1 or values.shape[0] != indices.shape[0] or \
+            tuple(int(d) for d in values.shape[1:]) != shape[1:]:
+        raise ValueError("values %s / indices %s do not fit dense_shape %s" %
+                         (tuple(values.shape), tuple(indices.shape), shape))
+    return values.contiguous(), indices.to(torch.int64).contiguous(), shape
+
+
+def sparse_allreduce(slices, op=None, prescale_factor=1.0, postscale_factor=1.0, coalesced=False):
+    """The dense sum of a sparse gradient over all ranks, by the ordered row-sum kernels
+    (tips_sparse_allreduce; DESIGN.md, Sparse allreduce).
+
+    `slices`: an IndexedSlices with dense_shape, or a torch sparse COO tensor whose first dimension
+    is the only sparse one. Device tensors of float32, float64, float16, bfloat16, int32 or int64.
+    Returns dense[j] = postscale_factor * (sum over the entries with index j of prescale_factor *
+    values[i]), the entries taken in ascending (rank, position) order and folded left to right in
+    fp32 (f64 for float64, the integer type for integers), rounded once: the same bits on every rank
+    and on every run; rows nothing names are +0. Entries whose index is outside [0, rows) are skipped
+    and counted (sparse_stats); under set_consistency_check(True) they raise ValueError after the
+    reduction (one synchronisation). With coalesced=True: an IndexedSlices of the ascending unique
+    indices (torch.unique of the gathered indices) and their summed rows, taken from the dense
+    result. op=Average divides by size() through the postscale factor, whatever set_op_scaling says;
+    op=Max / Min, an integer dtype with a factor (or op=Average), and host tensors raise ValueError
+    before anything is initialised."""
+    if op in (Max, Min):
+        raise ValueError("op=%s is not defined for sparse inputs: the row sum adds repeated indices" % op)
+    pre, post = float(prescale_factor), float(postscale_factor)
+    values, indices, shape = _sparse_parts(slices, op == Average or pre != 1.0 or post != 1.0)
+    code = _tensors.dtype_code(values)
+    import torch
+    init()
+    if op == Average:
+        post = post / size()
+    rows = shape[0]
+    row_elems = 1
+    for d in shape[1:]:
+        row_elems *= d
+    n = int(indices.shape[0])
+    with torch.cuda.device(values.device):
+        dense = torch.empty(shape, dtype=values.dtype, device=values.device)
+        _ops._lib.call("tips_sparse_allreduce", values.data_ptr() if n else None, indices.data_ptr() if n else None, n,
+                       rows, row_elems, code, pre, post, dense.data_ptr() if dense.numel() else None,
+                       _tensors.stream_of(values))
+        gathered = None
+        if _ops._check or coalesced:
+            gathered = allgather_op(indices) if size() > 1 else indices
+        if _ops._check and gathered.numel():
+            lo, hi = int(gathered.min()), int(gathered.max())
+            if lo < 0 or hi >= rows:
+                raise ValueError("sparse_allreduce: indices outside [0, %d) (min %d, max %d) were skipped" % (rows, lo, hi))
+        if not coalesced:
+            return dense
+        uniq = torch.unique(gathered)
+        uniq = uniq[(uniq >= 0) & (uniq < rows)]
+        return IndexedSlices(dense.index_select(0, uniq), uniq, dense_shape=shape)
+
+
+def sparse_stats():
+    """(calls, entries, bad_indices) of this process's row sums: launches, the entries they covered,
+    and the entries skipped for an index outside [0, rows). Synchronises the device."""
+    import ctypes
+    v = [ctypes.c_int64() for _ in range(3)]
+    _ops._lib.call("tips_sparse_stats", *[ctypes.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
+def _device_sparse(g):
+    """A sparse gradient sparse_allreduce takes: device values and indices, a dense shape, one sparse dimension."""
+    if isinstance(g, IndexedSlices):
+        return g.dense_shape is not None and _tensors.is_device(g.values) and _tensors.is_device(g.indices)
+    return _tensors.is_torch(g) and g.is_sparse and g.is_cuda and g.sparse_dim() == 1
+
+
 def _no_minmax_grads(op):
     if op in (Max, Min):
         raise ValueError("op=%s is not supported for gradient lists: the fused reductions carry SUM only "
@@ -198,11 +316,35 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     prescale 1/f before the sums, postscale f/size() after them.
     """
     _no_minmax_grads(op)
+    if sparse_as_dense and _sparse_reduce and compression is Compression.none and any(_device_sparse(g) for g in grads):
+        return _reduce_grads_sparse(grads, compression, op, fused, gradient_predivide_factor)
     if sparse_as_dense:
         grads = [_to_dense(g) if g is not None else g for g in grads]
     if size() <= 1:
         return list(grads)
     return _reduce_grads(grads, compression, op, fused, gradient_predivide_factor)
+
+
+def _reduce_grads_sparse(grads, compression, op, fused, gradient_predivide_factor):
+    """allreduce_grads(sparse_as_dense=True) under set_sparse_reduce(True): the device sparse
+    gradients go through sparse_allreduce, one call each - with the factors the dense route would
+    apply (_average_scale: op=Average divides only under set_op_scaling, as for the dense gradients
+    of the same list) - and come back dense and reduced; the rest of the list takes today's route."""
+    scale = _average_scale(op, gradient_predivide_factor) if size() > 1 else None
+    pre, post = scale if scale is not None else (1.0, 1.0)
+    out, rest = list(grads), []
+    for i, g in enumerate(grads):
+        if g is not None and _device_sparse(g):
+            out[i] = sparse_allreduce(g, prescale_factor=pre, postscale_factor=post)
+            rest.append(None)
+        else:
+            rest.append(_to_dense(g) if g is not None else g)
+    if size() > 1 and any(g is not None for g in rest):
+        rest = _reduce_grads(rest, compression, op, fused, gradient_predivide_factor)
+    for i, g in enumerate(rest):
+        if g is not None:
+            out[i] = g
+    return out
 
 
 def _average_scale(op, gradient_predivide_factor=1.0):

@@ -1486,6 +1486,15 @@ const char* master_addr() {
 
 bool on_negotiation_thread() { return tl_negotiation_thread; }
 
+bool negotiation_running() {
+  std::shared_ptr<Negotiator> n;
+  {
+    std::lock_guard<AdaptiveMutex> l(g_neg_mu);
+    n = g_neg;
+  }
+  return n && n->running();
+}
+
 int negotiation_stop() {
   std::shared_ptr<Negotiator> n;
   {

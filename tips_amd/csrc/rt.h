@@ -206,6 +206,13 @@ struct State {
   EventPool recv_ev, sum_ev;
   DevBuf staging, host_in, host_out, fusion, small;
   DevBuf cast_scratch;  // fusion.cc, fused casts: a list's tensors of at least the threshold, in the wire type
+  // sparse.cc, tips_sparse_allreduce: the gathered indices, the gathered values and the row-sum's
+  // workspace. One call at a time uses it (sparse_mu), and a call on another stream first waits for
+  // the event the previous call recorded behind its last launch.
+  DevBuf sparse_scratch;
+  std::mutex sparse_mu;
+  hipEvent_t ev_sparse = nullptr;
+  bool sparse_chain_valid = false;
   void* bounce_in = nullptr;  // page-locked kBounceBytes each (hipHostMalloc), for small pageable host tensors
   void* bounce_out = nullptr;
   HostPool* host_pool = nullptr;  // fused host tensors: pack / unpack threads
@@ -350,6 +357,9 @@ int list_collective(const void* const* ins, const int64_t* counts, int n, int dt
                     void* const* outs, void* flat, bool route, const ListBody& body);
 // Whether the calling thread is a negotiation thread (named requests and routed calls execute there)
 bool on_negotiation_thread();
+// Whether this rank's negotiation runs (synchronous collectives are then routed through it)
+bool negotiation_running();
+void sparse_release(State& st);  // sparse.cc (shutdown)
 
 // ---------------------------------------------------------------------------
 // host staging: the reference's ops work on host (TF CPU) tensors (ops.cc:88-90)
