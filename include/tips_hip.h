@@ -261,6 +261,60 @@ TIPS_API int tips_sparse_allreduce(const void* values, const int64_t* indices, i
  * bad_indices NULL nothing is synchronised). */
 TIPS_API int tips_sparse_stats(int64_t* calls, int64_t* entries, int64_t* bad_indices);
 
+/* ---- Adasum (Adasum allreduce) ---- */
+
+/* One definition for the calls below. A call reduces a list of SEGMENTS; a segment is one tensor, and
+ * a single-tensor call has one. For two operands a and b holding the same segments, for each segment
+ * s independently:
+ *     d  = SUM a_i b_i    na = SUM a_i a_i    nb = SUM b_i b_i       (over the elements of s, in f64)
+ *     ca = (na > 0) ? 1.0 - 0.5 (d / na) : 1.0                       (f64, every operation a separate IEEE op)
+ *     cb = (nb > 0) ? 1.0 - 0.5 (d / nb) : 1.0
+ *     out_i = round_S( fl_W( fl_W(ca_W a_i) + fl_W(cb_W b_i) ) )
+ * W is the working type - fp32 for FLOAT32 / FLOAT16 / BFLOAT16, f64 for FLOAT64 - ca_W / cb_W the
+ * coefficients rounded once from f64 to W, S the storage type: one rounding at the store. The
+ * threshold is exact zero (this project's definition). Non-finite values get no special handling: a
+ * NaN or an infinity anywhere in a segment of either operand makes that segment's whole result NaN;
+ * other segments are unaffected. The three sums are accumulated in f64 in an order that is a function
+ * of the segment's length and the dtype alone (DESIGN.md writes it down): alignment, the segment's
+ * place in the buffer, its neighbours, the grid and the schedule change no bit, and two runs give the
+ * same bits. Across p ranks, p a power of two, the result is the binary tree by recursive doubling:
+ * at level k = 0 ... log2(p) - 1 rank r pairs with rank r XOR 2^k, a = the value of the partner
+ * whose bit k is clear, b = the other's; both compute the same pair, so every rank ends with the
+ * same bits; 16-bit storage rounds to storage at every level. p = 1 is the copy. Integer dtypes
+ * return TIPS_ERR_UNSUPPORTED; there is no scaled Adasum; Adasum is not a tips_op and is never
+ * captured or replayed as a graph. Every pointer is a device pointer: a host pointer returns
+ * TIPS_ERR_UNSUPPORTED and is not staged. */
+
+/* Bytes of workspace tips_adasum_pair needs for `count` elements in `nseg` segments, whatever the
+ * float dtype: 8 * (3 * (count / 4096 + nseg) + 2 * nseg) rounded up to 256 (3 doubles per 32 KiB
+ * chunk of a segment, 2 coefficients per segment). < 0 = error. */
+TIPS_API int64_t tips_adasum_workspace(int64_t count, int nseg);
+/* The local operation: dst = ca a + cb b over nseg segments that lie back to back in dst, a and b
+ * (seg_counts[i] elements each, host array; their sum is the buffers' length). Stream-ordered, needs
+ * no tips_init (like tips_bucket_sum and tips_rows_sum). dst may be a or b; otherwise the buffers and
+ * the workspace must not overlap. Negative sizes and a workspace smaller than
+ * tips_adasum_workspace(total, nseg) (or not 8-B aligned) return TIPS_ERR_INVALID_ARG, an integer
+ * dtype TIPS_ERR_UNSUPPORTED; a total of 0 is TIPS_OK with nothing launched, and a segment of length 0
+ * is legal and writes nothing. A list of more than one segment is uploaded as a table the first time
+ * its counts are seen (that call synchronises with the device) and reused afterwards. */
+TIPS_API int tips_adasum_pair(void* dst, const void* a, const void* b, const int64_t* seg_counts, int nseg, int dtype,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+/* The collective over one tensor (one segment), out of place or in place (in == out),
+ * stream-ordered: per level one RCCL send / recv of the whole buffer with the partner into runtime
+ * scratch, then the pair on the same stream. The ranks first compare {tensors, elements, dtype, a hash
+ * of the counts} on the host (the gather behind tips_allgather_i64): a difference returns
+ * TIPS_ERR_MISMATCH on every rank before any device exchange. A rank count that is no power of two
+ * returns TIPS_ERR_UNSUPPORTED on every rank, as does TIPS_ALGO_PEER; every other algorithm setting
+ * is ignored (Adasum has its one schedule). While a negotiation runs (after the first named request)
+ * it returns TIPS_ERR_UNSUPPORTED: named Adasum requests are not implemented. */
+TIPS_API int tips_allreduce_adasum(const void* in, void* out, int64_t count, int dtype, void* stream);
+/* The collective over a list: the n tensors are packed into `flat` at tips_fused_layout's offsets (the
+ * pack launch of tips_fused_allreduce_flat), and the levels run over the whole flat buffer with one
+ * segment per tensor - the padding between tensors travels with the buffer and is never part of a
+ * segment. The same checks and refusals as tips_allreduce_adasum. */
+TIPS_API int tips_fused_allreduce_adasum_flat(const void* const* ins, const int64_t* counts, int n, int dtype,
+                                              void* flat, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

@@ -14,6 +14,7 @@ from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadc
                   fused_allreduce_, rank_op, registered_host_buffer, set_algorithm, set_consistency_check, size_op)
 from .ops import fused_allreduce_cast, fused_allreduce_flat, fused_allreduce_host, fused_allreduce_host_flat, fusion_stats
 from .ops import set_op_scaling, allreduce_reduce_op
+from .ops import adasum_op, fused_adasum_flat
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
@@ -22,6 +23,7 @@ Average = 'Average'
 Sum = 'Sum'
 Min = 'Min'
 Max = 'Max'
+Adasum = 'Adasum'
 
 
 class IndexedSlices(object):
@@ -43,6 +45,7 @@ __all__ = [
     "DistributedOptimizer", "DistributedGradientTape", "fused_allreduce_cast", "fused_allreduce_flat", "fused_allreduce_host", "fused_allreduce_host_flat", "fusion_stats",
     "allreduce_scaled", "set_op_scaling", "Min", "Max", "allreduce_reduce_op",
     "sparse_allreduce", "set_sparse_reduce", "sparse_stats",
+    "Adasum", "adasum_op", "fused_adasum_flat",
 ]
 
 
@@ -107,9 +110,20 @@ def allreduce(tensor,
     `compression` composes as for the sum. They raise ValueError with a scale
     factor other than 1, a sparse input or a `name` (named requests carry SUM
     only).
+
+    op=Adasum returns the Adasum of the ranks' tensors (ops.adasum_op ->
+    tips_allreduce_adasum), whatever set_op_scaling says: the
+    binary tree over a power-of-two number of ranks of ca a + cb b with
+    ca = 1 - a.b / (2 a.a), cb = 1 - a.b / (2 b.b), the dot products over the
+    whole tensor in f64. Dense device float tensors; `compression` composes as
+    for the sum (the tree then runs in the compressed dtype). It raises
+    ValueError with a scale factor other than 1, a `name`, a sparse input, an
+    integer dtype or a host tensor.
     """
     if op in (Max, Min):
         return _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name)
+    if op == Adasum:
+        return _allreduce_adasum(tensor, compression, prescale_factor, postscale_factor, name)
     if isinstance(tensor, IndexedSlices):
         values = allgather_op(tensor.values)
         indices = allgather_op(tensor.indices)
@@ -147,6 +161,48 @@ def _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor
         raise ValueError("op=%s takes no name: named requests go through the negotiation, which carries SUM only" % op)
     tensor_compressed, ctx = compression.compress(tensor)
     return compression.decompress(allreduce_reduce_op(tensor_compressed, op), ctx)
+
+
+def _allreduce_adasum(tensor, compression, prescale_factor, postscale_factor, name):
+    """allreduce(op=Adasum): the argument checks (before anything is initialised), then compress,
+    reduce, decompress."""
+    if float(prescale_factor) != 1.0 or float(postscale_factor) != 1.0:
+        raise ValueError("op=Adasum takes no prescale_factor / postscale_factor: there is no scaled Adasum")
+    if name is not None:
+        raise ValueError("op=Adasum takes no name: named requests go through the negotiation, which carries SUM only")
+    if isinstance(tensor, IndexedSlices):
+        raise ValueError("op=Adasum is not defined for sparse inputs: densify first")
+    _ops.check_adasum_tensor(tensor)
+    tensor_compressed, ctx = compression.compress(tensor)
+    return compression.decompress(adasum_op(tensor_compressed), ctx)
+
+
+def _adasum_grads(grads, compression, fused):
+    """allreduce_grads(op=Adasum) at N > 1: the argument checks for the whole list first, then the
+    dense device float gradients per (dtype, device) through fused_adasum_flat, each gradient a segment
+    of its own (fused=False: one adasum_op each). With a compression every gradient is compressed on
+    its own, the compressed list is reduced, and every result decompressed (unfused casts)."""
+    for g in grads:
+        if g is None:
+            continue
+        if isinstance(g, IndexedSlices):
+            raise ValueError("op=Adasum is not defined for sparse gradients: densify first")
+        _ops.check_adasum_tensor(g, "allreduce_grads(op=Adasum)")
+    out = list(grads)
+    groups = {}
+    for i, g in enumerate(grads):
+        if g is None:
+            continue
+        c, ctx = compression.compress(g)
+        c = c if c.is_contiguous() else c.contiguous()
+        if not fused:
+            out[i] = compression.decompress(adasum_op(c), ctx)
+            continue
+        groups.setdefault((c.dtype, c.device), []).append((i, c, ctx))
+    for members in groups.values():
+        for (i, _, ctx), s in zip(members, fused_adasum_flat([c for _, c, _ in members])):
+            out[i] = compression.decompress(s, ctx)
+    return out
 
 
 _sparse_reduce = _os.environ.get("TIPS_SPARSE_REDUCE", "0") == "1"
@@ -314,8 +370,24 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     tips_scale per output buffer (unfused); host tensors one scaled allreduce
     each. gradient_predivide_factor f (op=Average only) splits the division:
     prescale 1/f before the sums, postscale f/size() after them.
+
+    op=Adasum takes effect whatever set_op_scaling says: dense device float
+    gradients go per (dtype, device) through fused_adasum_flat, each gradient
+    a segment with its own coefficients (fused=False: one adasum_op each);
+    None entries and size() == 1 pass through as for the sum. Under
+    Compression.fp16 each gradient is compressed, the list is reduced in
+    float16 and each result decompressed - unfused casts, one launch per
+    gradient each way. Host or sparse gradients raise ValueError.
     """
     _no_minmax_grads(op)
+    if op == Adasum:
+        if gradient_predivide_factor != 1.0:
+            raise ValueError("gradient_predivide_factor not supported with op != Average")
+        if sparse_as_dense:
+            grads = [_to_dense(g) if g is not None else g for g in grads]
+        if size() <= 1:
+            return list(grads)
+        return _adasum_grads(grads, compression, fused)
     if sparse_as_dense and _sparse_reduce and compression is Compression.none and any(_device_sparse(g) for g in grads):
         return _reduce_grads_sparse(grads, compression, op, fused, gradient_predivide_factor)
     if sparse_as_dense:

@@ -102,6 +102,14 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
       ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     ("tips_sparse_stats", ctypes.c_int, [_c_i64_p, _c_i64_p, _c_i64_p]),
+    ("tips_adasum_workspace", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    ("tips_adasum_pair", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+      ctypes.c_int64, ctypes.c_void_p]),
+    ("tips_allreduce_adasum", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
+    ("tips_fused_allreduce_adasum_flat", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

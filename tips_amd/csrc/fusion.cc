@@ -914,6 +914,22 @@ int fused_allreduce_flat(State& st, const BatchItem* items, int n, int dtype, vo
   });
 }
 
+// The flat call's pack alone, at any number of ranks: every tensor copied to its layout offset in
+// `flat` by one launch over the whole space (adasum.cc reduces the flat buffer itself).
+int fused_pack_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t user) {
+  if (n <= 0) return 0;
+  FusionCache& fc = cache(st);
+  return in_fusion(st, user, [&](hipStream_t ws) -> int {
+    Layout* L = nullptr;
+    TRY(open_layout(st, fc, items, n, dtype, layout_params(), ws, &L));
+    if (!L) return TIPS_ERR_HIP;
+    if (L->seg_tensor.empty()) return 0;
+    Table* t = find_table(st, fc, *L, kFlat, items, n, flat);
+    if (!t) return TIPS_ERR_HIP;
+    return copy_tiles(*L, *t, 0, 0, L->ntiles, ws);
+  });
+}
+
 int fused_allreduce_cast(State& st, const BatchItem* items, int n, int wire, hipStream_t user) {
   if (n <= 0) return 0;
   FusionCache& fc = cache(st);

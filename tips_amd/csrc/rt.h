@@ -213,6 +213,12 @@ struct State {
   std::mutex sparse_mu;
   hipEvent_t ev_sparse = nullptr;
   bool sparse_chain_valid = false;
+  // adasum.cc, the Adasum collectives: the partner's buffer, then the pair's workspace (partials and
+  // coefficients). One call at a time (adasum_mu), chained across calling streams like the sparse scratch.
+  DevBuf adasum_scratch;
+  std::mutex adasum_mu;
+  hipEvent_t ev_adasum = nullptr;
+  bool adasum_chain_valid = false;
   void* bounce_in = nullptr;  // page-locked kBounceBytes each (hipHostMalloc), for small pageable host tensors
   void* bounce_out = nullptr;
   HostPool* host_pool = nullptr;  // fused host tensors: pack / unpack threads
@@ -360,6 +366,10 @@ bool on_negotiation_thread();
 // Whether this rank's negotiation runs (synchronous collectives are then routed through it)
 bool negotiation_running();
 void sparse_release(State& st);  // sparse.cc (shutdown)
+void adasum_release(State& st);  // adasum.cc (shutdown: the scratch and the cached segment tables)
+// fusion.cc: the flat call's pack alone - every tensor of the list copied to its fused_layout offset
+// in `flat` (items[i].out = flat), one launch, in the fusion chain. Caller holds st.mu.
+int fused_pack_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // host staging: the reference's ops work on host (TF CPU) tensors (ops.cc:88-90)

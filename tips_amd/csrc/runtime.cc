@@ -130,6 +130,7 @@ void tips_shutdown(void) {
   st.small.release();
   st.cast_scratch.release();
   sparse_release(st);
+  adasum_release(st);
   st.tuned.clear();
   st.recv_ev.release();
   st.sum_ev.release();

@@ -581,6 +581,56 @@ def _out_ptrs(fo, flat):
     return hit[1]
 
 
+_ADASUM_FLOATS = (_lib.FLOAT32, _lib.FLOAT64, _lib.FLOAT16, _lib.BFLOAT16)
+
+
+def check_adasum_tensor(t, what="op=Adasum"):
+    """The dtype code of a tensor Adasum takes - a dense device float tensor - or ValueError; touches
+    no library state."""
+    if tensors.is_torch(t) and t.is_sparse:
+        raise ValueError("%s is not defined for sparse inputs: densify first" % what)
+    code = tensors.dtype_code(t)
+    if code not in _ADASUM_FLOATS:
+        raise ValueError("%s is defined for float dtypes only (got %s)" % (what, t.dtype))
+    if not tensors.is_device(t):
+        raise ValueError("%s takes device tensors only (host tensors are not staged)" % what)
+    return code
+
+
+def adasum_op(tensor):
+    """Adasum of `tensor` over all ranks, out of place (tips_allreduce_adasum): the
+    binary tree by recursive doubling of out = ca a + cb b, ca = 1 - d / (2 na), cb = 1 - d / (2 nb)
+    with the dot products d, na, nb accumulated in f64 over the whole tensor. A power-of-two number
+    of ranks; one rank returns a copy. A dense device float tensor; stream-ordered."""
+    code = check_adasum_tensor(tensor, "adasum_op")
+    basics.init()
+    src = tensors.contiguous(tensor)
+    out = tensors.empty_like(src)
+    n = tensors.numel(src)
+    if n:
+        _lib.call("tips_allreduce_adasum", tensors.data_ptr(src), tensors.data_ptr(out), n, code, tensors.stream_of(src))
+    return out
+
+
+def fused_adasum_flat(tensor_list):
+    """Adasum of a list of same-dtype device float tensors, each tensor a segment of its own - its own
+    dot products and coefficients (tips_fused_allreduce_adasum_flat): the list is packed into one flat
+    buffer laid out as fused_allreduce_flat's and reduced there, log2(size()) exchanges of the whole
+    buffer. The outputs are views of that buffer, reused like fused_allreduce_flat's. Inputs unchanged."""
+    if not tensor_list:
+        return []
+    for t in tensor_list:
+        check_adasum_tensor(t, "fused_adasum_flat")
+    basics.init()
+    code = _check_fusable(tensor_list, "fused_adasum_flat")
+    fo = _flat_outputs(tensor_list, code)
+    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+    flat, views = fo.take()
+    _lib.call("tips_fused_allreduce_adasum_flat", pp[0], fo.cp[0], len(tensor_list), code, flat.data_ptr(),
+              _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+    return views
+
+
 def _flat_call(tensor_list, code, ptrs, scale=None):
     return _flat_run(_flat_outputs(tensor_list, code), tensor_list, ptrs, scale)
 

@@ -640,6 +640,10 @@ def DistributedOptimizer(optimizer,
     torch.optim.Optimizer. name / use_locking / device_* are accepted for signature compatibility.
     Under set_op_scaling(True), op=Average (the default) divides by size() inside the reduction and
     gradient_predivide_factor f moves 1/f of it before the sums (for 16-bit gradients)."""
+    if op == 'Adasum':
+        raise ValueError('op=Adasum is not supported by DistributedOptimizer: Horovod applies Adasum there to weight '
+                         'deltas, not gradients, and that wrapper is not implemented. Reduce gradients with '
+                         'allreduce_grads(grads, op=Adasum) or DistributedGradientTape(op=Adasum)')
     groups = _validate(op, gradient_predivide_factor, num_groups, groups)
     try:
         import torch
