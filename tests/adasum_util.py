@@ -8,7 +8,7 @@ import math
 
 import numpy as np
 
-from gpu_util import BF16, F16, F32, F64, NPDT
+from gpu_util import BF16, F16, F32, F64, NPDT, rand
 
 CHUNK_BYTES = 32768  # of each operand per chunk: 256 lanes x 8 vectors of 16 B
 LANES, VECS = 256, 8
@@ -62,17 +62,17 @@ def _tree256(v):
     return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
 
 
-def segment_dots(a, b, dtype):
-    """(d, na, nb) of one segment in the kernels' order. Element i belongs to chunk i // K and to lane
+def chunk_partials(a, b, dtype, tree=_tree256):
+    """The (m, 3) chunk sums (d, na, nb) of one segment of m chunks in the kernels' order - what the
+    dots pass leaves in the workspace. Element i belongs to chunk i // K and to lane
     (i % K // E) % 256 of it; a lane adds its products in ascending i from +0; a chunk's 256 lane
-    sums go through _tree256; lane t of the coefficient pass adds chunk sums t, t + 256, ... from +0
-    and those 256 go through _tree256 again. (Zero padding is bit-neutral: an accumulator that
-    started at +0 is never -0, and x + 0 = x.)"""
+    sums go through `tree`. (Zero padding is bit-neutral: an accumulator that started at +0 is never
+    -0, and x + 0 = x.)"""
     E, K = 16 // ES[dtype], chunk_elems(dtype)
     n = len(a)
     m = -(-n // K)
     if m == 0:
-        return 0.0, 0.0, 0.0
+        return np.zeros((0, 3), np.float64)
     x = np.zeros(m * K, np.float64)
     y = np.zeros(m * K, np.float64)
     x[:n], y[:n] = to_f64(a, dtype), to_f64(b, dtype)
@@ -87,16 +87,30 @@ def segment_dots(a, b, dtype):
                 acc[0] = acc[0] + xs * ys
                 acc[1] = acc[1] + xs * xs
                 acc[2] = acc[2] + ys * ys
-        c = _tree256(acc)  # (3, m)
-        rows = -(-m // LANES)
-        cp = np.zeros((3, rows * LANES), np.float64)
-        cp[:, :m] = c
-        cp = cp.reshape(3, rows, LANES)
-        lane = np.zeros((3, LANES), np.float64)
+        return np.ascontiguousarray(tree(acc).T)
+
+
+def fold_chunks(c, tree=_tree256):
+    """(d, na, nb) from a segment's (m, 3) chunk sums, the coefficient pass's order: lane t adds chunk
+    sums t, t + 256, ... from +0 and the 256 lane sums go through `tree`."""
+    m = len(c)
+    if m == 0:
+        return 0.0, 0.0, 0.0
+    rows = -(-m // LANES)
+    cp = np.zeros((3, rows * LANES), np.float64)
+    cp[:, :m] = c.T
+    cp = cp.reshape(3, rows, LANES)
+    lane = np.zeros((3, LANES), np.float64)
+    with np.errstate(all="ignore"):
         for r in range(rows):
             lane = lane + cp[:, r, :]
-        t = _tree256(lane)
+        t = tree(lane)
     return float(t[0]), float(t[1]), float(t[2])
+
+
+def segment_dots(a, b, dtype):
+    """(d, na, nb) of one segment in the kernels' order: chunk_partials, then fold_chunks."""
+    return fold_chunks(chunk_partials(a, b, dtype))
 
 
 def coefficients(d, na, nb):
@@ -132,6 +146,54 @@ def pair_ref(a, b, seg_counts, dtype, dots=segment_dots):
         ca, cb = coefficients(*dots(a[lo:hi], b[lo:hi], dtype))
         out[lo:hi] = combine(a[lo:hi], b[lo:hi], ca, cb, dtype)
     return out
+
+
+def pair_intermediates(a, b, seg_counts, dtype):
+    """What a pair call leaves in its workspace: the call's chunk sums, (nchunks, 3) f64 in global
+    chunk order (an empty segment has none), and the per-segment (ca, cb), (nseg, 2) f64."""
+    assert len(a) == len(b) == sum(seg_counts)
+    parts, coef = [np.zeros((0, 3), np.float64)], np.empty((len(seg_counts), 2), np.float64)
+    for s, (lo, hi) in enumerate(segments(seg_counts)):
+        c = chunk_partials(a[lo:hi], b[lo:hi], dtype)
+        parts.append(c)
+        coef[s] = coefficients(*fold_chunks(c))
+    return np.concatenate(parts), coef
+
+
+def shape_counts(dtype):
+    """The single-segment sizes at which the launch shape changes: 128 chunks (the last grid on
+    contiguous eighths), 129 (the first striped grid, a one-element last chunk), 256 (the last
+    one-row coefficient pass) and 257 (its second row; one whole vector and one element in the last chunk)."""
+    K, E = chunk_elems(dtype), 16 // ES[dtype]
+    return [128 * K, 128 * K + 1, 256 * K, 256 * K + E + 1]
+
+
+def long_count(dtype):
+    return shape_counts(dtype)[-1]
+
+
+def seeded_pair(dtype, counts, salt=0, along=0.0):
+    """The seeded normal operands (a, b) of a test case: the GPU tests and the CPU tests that vouch for
+    them draw the same ones. along != 0: b = along a + a quarter of the independent draw."""
+    rng = np.random.default_rng([20261020, dtype, salt, len(counts), sum(counts)])
+    n = sum(counts)
+    a, b = rand(dtype, n, rng), rand(dtype, n, rng)
+    if along:
+        W = to_work(a, dtype).dtype.type
+        b = round_store(W(along) * to_work(a, dtype) + W(0.25) * to_work(b, dtype), dtype)
+    return a, b
+
+
+# Independent operands hide the dots' last bits from the coefficients: d / na is near 0 and
+# 1 - 0.5 (d / na) rounds them away. With b near 2 a, d / na is near 2 and ca = 1 - 0.5 (d / na) is an
+# exact difference that keeps every bit of the quotient, so a dot product off by an ulp shows in
+# ca's f64 bits. The salts are those at which both wrong orders of test_adasum_cpu.py do show.
+LONG_SALT = {F32: 4, F64: 0, F16: 1, BF16: 0}
+
+
+def long_pair(dtype, count):
+    """The operands of the single-segment launch-shape cases (shape_counts)."""
+    return seeded_pair(dtype, [count], LONG_SALT[dtype], along=2.0)
 
 
 def tree_ref(values, seg_counts, dtype, pair=pair_ref):

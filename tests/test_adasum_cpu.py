@@ -9,8 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from adasum_util import (chunk_elems, coefficients, free_ref, pair_ref, segment_dots, to_f64, tree_ref, within_bound,
-                         workspace_bytes)
+from adasum_util import (ES, LANES, VECS, _tree256, chunk_elems, chunk_partials, coefficients, fold_chunks, free_ref,
+                         long_count, long_pair, pair_intermediates, pair_ref, seeded_pair, segment_dots, segments, to_f64,
+                         tree_ref, within_bound, workspace_bytes)
 from conftest import REPO
 from gpu_util import BF16, F16, F32, F64, I32, I64, NPDT, bits, rand, same_bits
 
@@ -51,6 +52,116 @@ def test_order_is_a_real_one(dtype):
         fold += v
     assert na != fold
     assert abs(na - fold) <= 1e-12 * fold
+
+
+def _reference_dots(a, b, dtype):
+    """segment_dots as it stood before chunk_partials was split out of it, kept to pin the bits."""
+    E, K = 16 // ES[dtype], chunk_elems(dtype)
+    n = len(a)
+    m = -(-n // K)
+    if m == 0:
+        return 0.0, 0.0, 0.0
+    x = np.zeros(m * K, np.float64)
+    y = np.zeros(m * K, np.float64)
+    x[:n], y[:n] = to_f64(a, dtype), to_f64(b, dtype)
+    x, y = x.reshape(m, VECS, LANES, E), y.reshape(m, VECS, LANES, E)
+    acc = np.zeros((3, m, LANES), np.float64)
+    for u in range(VECS):
+        for j in range(E):
+            xs, ys = x[:, u, :, j], y[:, u, :, j]
+            acc[0] = acc[0] + xs * ys
+            acc[1] = acc[1] + xs * xs
+            acc[2] = acc[2] + ys * ys
+    c = _tree256(acc)
+    rows = -(-m // LANES)
+    cp = np.zeros((3, rows * LANES), np.float64)
+    cp[:, :m] = c
+    cp = cp.reshape(3, rows, LANES)
+    lane = np.zeros((3, LANES), np.float64)
+    for r in range(rows):
+        lane = lane + cp[:, r, :]
+    return tuple(float(v) for v in _tree256(lane))
+
+
+@pytest.mark.parametrize("dtype", FLOATS)
+@pytest.mark.parametrize("counts", [[1], [63], [64], [65], [4099], [262147], LIST])
+def test_segment_dots_is_built_on_chunk_partials_bit_for_bit(dtype, counts):
+    """The split changed no bit: per segment, segment_dots = fold_chunks(chunk_partials) = the
+    unsplit computation; pair_intermediates holds the same chunk sums in global chunk order and the
+    coefficients pair_ref uses."""
+    rng = np.random.default_rng(100 * dtype + len(counts) + counts[0] % 7)
+    a, b = rand(dtype, sum(counts), rng), rand(dtype, sum(counts), rng)
+    parts, coef = pair_intermediates(a, b, counts, dtype)
+    K = chunk_elems(dtype)
+    assert parts.shape == (sum(-(-c // K) for c in counts), 3) and coef.shape == (len(counts), 2)
+    c0 = 0
+    for s, (lo, hi) in enumerate(segments(counts)):
+        dots = segment_dots(a[lo:hi], b[lo:hi], dtype)
+        assert np.array_equal(bits(np.array(dots)), bits(np.array(_reference_dots(a[lo:hi], b[lo:hi], dtype))))
+        c = chunk_partials(a[lo:hi], b[lo:hi], dtype)
+        assert c.shape == (-(-(hi - lo) // K), 3) and c.dtype == np.float64
+        assert np.array_equal(bits(np.array(fold_chunks(c))), bits(np.array(dots)))
+        assert np.array_equal(bits(parts[c0:c0 + len(c)]), bits(c))
+        assert np.array_equal(bits(coef[s]), bits(np.array(coefficients(*dots))))
+        c0 += len(c)
+    assert c0 == len(parts)
+    assert np.array_equal(coef[[c == 0 for c in counts]], np.ones((counts.count(0), 2)))
+
+
+@pytest.mark.parametrize("dtype", FLOATS)
+@pytest.mark.parametrize("chunks", [257, 300])
+def test_second_row_of_the_coefficient_pass_inside_the_bound(dtype, chunks):
+    """More than 256 chunks: lane t of the coefficient pass adds a second chunk sum (rows = 2 in
+    fold_chunks). The restatement stays inside the order-free reference's bound there.
+    Independent operands, as in every use of that bound: it takes the coefficients as exact to one
+    rounding, which holds while they are near 1, and the store as a relative error, which holds
+    above the subnormals. The launch-shape cases' operands (long_pair: b near 2 a, so ca is an
+    exact difference near 4e-5 whose relative error is that of d / na times 1e5, and 0.75 b_i lands
+    among f16's subnormals) are made to show the dots' last ulp in ca; the bound says nothing there."""
+    n = (chunks - 1) * chunk_elems(dtype) + 16 // ES[dtype] + 1
+    assert chunks != 257 or n == long_count(dtype)
+    a, b = seeded_pair(dtype, [n])
+    assert len(chunk_partials(a[:1], b[:1], dtype)) == 1 and len(chunk_partials(a, b, dtype)) == chunks
+    ref, bound = free_ref(a, b, [n], dtype)
+    assert within_bound(pair_ref(a, b, [n], dtype), ref, bound, dtype)
+
+
+def _tree256_low(v):
+    """A wrong wave tree: folded from the low half (x[l] += x[l + 1] first, x[l] += x[l + 32] last)."""
+    v = v.reshape(v.shape[:-1] + (4, 64))
+    while v.shape[-1] > 1:
+        v = v[..., 0::2] + v[..., 1::2]
+    w = v[..., 0]
+    return ((w[..., 0] + w[..., 1]) + w[..., 2]) + w[..., 3]
+
+
+def _dots_chunks_left_to_right(a, b, dtype):
+    """A wrong coefficient pass: the chunk sums added c_0 + c_1 + ... in one accumulator."""
+    acc = np.zeros(3, np.float64)
+    for c in chunk_partials(a, b, dtype):
+        acc = acc + c
+    return tuple(acc)
+
+
+def _dots_low_tree(a, b, dtype):
+    return fold_chunks(chunk_partials(a, b, dtype, tree=_tree256_low), tree=_tree256_low)
+
+
+@pytest.mark.parametrize("dtype", FLOATS)
+@pytest.mark.parametrize("wrong", [_dots_chunks_left_to_right, _dots_low_tree], ids=["chunks_left_to_right", "low_half_tree"])
+def test_order_is_visible_in_the_coefficients_at_257_chunks(dtype, wrong):
+    """The operands test_gpu_adasum_shapes.py runs at 257 chunks tell the kernels' order from two
+    other plausible ones in the f64 bits of (d, na, nb) and - what the device test can read, the
+    workspace keeping no segment sums - in those of (ca, cb), so the device comparison of the
+    coefficients can fail; all of them agree to a few ulps. (b is near 2 a there: see
+    adasum_util.LONG_SALT. With independent operands the dots differ as well, and the coefficients,
+    near 1, round the difference away.)"""
+    n = long_count(dtype)
+    a, b = long_pair(dtype, n)
+    right, other = np.array(segment_dots(a, b, dtype)), np.array(wrong(a, b, dtype))
+    assert not np.array_equal(bits(right), bits(other))
+    assert np.all(np.abs(right - other) <= 1e-12 * np.abs(right[1:]).max())
+    assert not np.array_equal(bits(np.array(coefficients(*right))), bits(np.array(coefficients(*other))))
 
 
 @pytest.mark.parametrize("dtype", FLOATS)

@@ -4,7 +4,12 @@ wave, a vector and a chunk, and a list with a segment below a wave, an empty one
 several chunks - and inside the definition's bound of the order-free reference. Then what holds
 without any restatement: a == b returns a, disjoint supports return tips_bucket_sum's bits, in place
 equals out of place, an unaligned view equals its aligned copy, a list equals its segments one by
-one, two runs agree; edge values; and, at one rank, the collectives' copy and lifecycle."""
+one, two runs agree; edge values; and, at one rank, the collectives' copy and lifecycle.
+
+Everything here stays within one round of XCD stripes (at most 65 chunks) and judges the output alone.
+Shapes beyond that - more than 128 chunks (the striped chunk map), more than 256 (the coefficient
+pass's second row), lists on the vector path, mixed alignment - with the workspace's partial sums and
+f64 coefficients compared too, further edge values and the layout cache: test_gpu_adasum_shapes.py."""
 import numpy as np
 import pytest
 
