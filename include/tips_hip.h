@@ -315,6 +315,67 @@ TIPS_API int tips_allreduce_adasum(const void* in, void* out, int64_t count, int
 TIPS_API int tips_fused_allreduce_adasum_flat(const void* const* ins, const int64_t* counts, int n, int dtype,
                                               void* flat, void* stream);
 
+/* ---- MXFP8 wire (MXFP8 wire compression) ---- */
+
+/* One definition for the calls below. The operand is a list of FLOAT32 device tensors laid out as
+ * tips_fused_layout(counts, n, TIPS_FLOAT32, offsets) says (a single tensor is a list of one);
+ * E = flat bytes / 4 elements. A BLOCK is 32 consecutive elements of that flat layout; tensors start
+ * on multiples of 64 elements, so no block straddles two tensors, and a tensor's last block may be
+ * partial: positions that hold no tensor element count as +0. The WIRE BUFFER of E elements holds one
+ * payload byte per element (OCP e4m3fn) at byte i and one scale byte per block at byte
+ * round_up(E, 256) + i / 32; it is round_up(E, 256) + round_up(E / 32, 256) bytes (tips_mxfp8_wire_bytes).
+ *   Quantise, per block x_0 ... x_31: (1) any NaN or +-Inf poisons the block: scale byte 0xFF, all 32
+ * payload bytes 0x7F, no other block affected. (2) Otherwise amax = max |x_j| with f32 biased exponent
+ * be and fraction fr gives e = max(be, 1) - 127, s = e - 8 + (fr > 0x600000 ? 1 : 0) clamped to
+ * [-127, 119], s = -127 for amax == 0; the scale byte is s + 127 (0 ... 246). (3) v_j = x_j * 2^-s as one
+ * f32 multiply, |v_j| clamped to 448 (which binds only for amax > 448 * 2^119), rounded to nearest
+ * even onto the e4m3fn grid, the sign kept (-0 -> 0x80). (4) Every payload and scale byte of the wire
+ * buffer is written, padding positions and alignment tails as zeros with scale byte 0.
+ *   Dequantise: y = decode_e4m3fn(byte) * 2^(scale byte - 127), one IEEE f32 multiply for every scale
+ * byte 0 ... 254 (subnormals honoured, overflow to +-Inf); scale byte 255, and the payload codes 0x7F /
+ * 0xFF, give NaN. With factor != 1 one further f32 multiply y * (float)factor follows. Every NaN is
+ * written as 0x7FC00000.
+ *   Fold of sources 0 ... k-1 over a block: every source dequantised (factor 1), acc = ((y0 + y1) + y2)
+ * + ... as separate f32 adds in source order, then acc quantised: a poisoned source block or a sum
+ * that is not finite poisons the result block by rule (1).
+ *   Collective over ranks 0 ... p-1: result = dequantise(quantise(fold in rank order of quantise(x_r)),
+ * factor): every rank decodes the same bytes, so every rank gets the same bits on every run; p = 1 is
+ * the round trip dequantise(quantise(x)). A block with amax below 2^-137 decodes to zeros, one with
+ * amax above 448 * 2^119 saturates its largest elements. Every pointer is a device pointer: a host
+ * pointer returns TIPS_ERR_UNSUPPORTED and is not staged; tensors are 4-B aligned, wire buffers 16-B. */
+
+/* Bytes of the wire buffer of `flat_elems` elements; *scales_offset (may be NULL) = the first scale
+ * byte's offset, round_up(flat_elems, 256). Pure host. < 0 = error. */
+TIPS_API int64_t tips_mxfp8_wire_bytes(int64_t flat_elems, int64_t* scales_offset);
+/* The three local operations: stream-ordered, no tips_init needed (like tips_bucket_sum). Negative
+ * sizes, nsrc outside 1 ... 16, a block range outside the buffer and a factor that is not a finite
+ * float return TIPS_ERR_INVALID_ARG; a total of 0 elements (or 0 blocks) is TIPS_OK with nothing
+ * launched, and an empty tensor inside a list is legal. `wire` must not overlap the tensors.
+ * tips_mxfp8_quantize writes the whole wire buffer of the list ins[0 .. n). tips_mxfp8_fold writes
+ * blocks [block_begin, block_begin + block_count) of dst_wire - payload and scale bytes, nothing
+ * else - from the same blocks of the nsrc source wire buffers of flat_elems elements each; dst_wire
+ * may be one of its sources. tips_mxfp8_dequantize writes the tensors outs[0 .. n) (their own
+ * elements only) from the list's wire buffer. */
+TIPS_API int tips_mxfp8_quantize(const void* const* ins, const int64_t* counts, int n, void* wire, void* stream);
+TIPS_API int tips_mxfp8_fold(void* dst_wire, const void* const* src_wires, int nsrc, int64_t flat_elems,
+                             int64_t block_begin, int64_t block_count, void* stream);
+TIPS_API int tips_mxfp8_dequantize(void* const* outs, const int64_t* counts, int n, const void* wire, double factor,
+                                   void* stream);
+/* The collective over one tensor, out of place or in place (in == out), ordered on the caller's
+ * stream: quantise into runtime scratch; the blocks cut into p contiguous chunks of whole blocks (a
+ * function of (E, p) alone, payload chunks 256-B aligned); one RCCL group sends chunk q to rank q and
+ * receives every peer's chunk `rank`; the fold of the p sources in rank order; one group gathers the
+ * reduced chunks; dequantise with `factor`. The ranks first compare {tensors, elements, a hash of the
+ * counts} on the host (the gather behind tips_allgather_i64): a difference returns TIPS_ERR_MISMATCH
+ * on every rank before any device exchange. More than 16 ranks, TIPS_ALGO_PEER, a stream that is
+ * being captured, and a running negotiation (named MXFP8 requests are not implemented) return
+ * TIPS_ERR_UNSUPPORTED; every other algorithm setting is ignored. */
+TIPS_API int tips_allreduce_mxfp8(const void* in, void* out, int64_t count, double factor, void* stream);
+/* The collective over a list: tensor i's result at tips_fused_layout's offset i of `flat` (the
+ * padding between tensors is not written). The same checks and refusals as tips_allreduce_mxfp8. */
+TIPS_API int tips_fused_allreduce_mxfp8_flat(const void* const* ins, const int64_t* counts, int n, void* flat,
+                                             double factor, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

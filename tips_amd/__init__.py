@@ -9,12 +9,14 @@ libtips_hip.so (include/tips_hip.h); there is no CPU fallback.
 import os as _os
 
 from .basics import TipsBasics, init, is_initialized, rank, shutdown, size
-from .compression import Compression, Compressor, FP16Compressor, NoneCompressor
+from .compression import Compression, Compressor, FP16Compressor, MXFP8Compressor, NoneCompressor
 from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadcast_async, allreduce_async_many, synchronize_many, allreduce_op, broadcast_op, poll, synchronize, broadcast_variables, bucket_sum, fused_allreduce,
                   fused_allreduce_, rank_op, registered_host_buffer, set_algorithm, set_consistency_check, size_op)
 from .ops import fused_allreduce_cast, fused_allreduce_flat, fused_allreduce_host, fused_allreduce_host_flat, fusion_stats
 from .ops import set_op_scaling, allreduce_reduce_op
 from .ops import adasum_op, fused_adasum_flat
+from .ops import (allreduce_mxfp8, fused_allreduce_mxfp8, mxfp8_dequantize, mxfp8_fold, mxfp8_quantize,
+                  mxfp8_wire_bytes)
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
@@ -46,6 +48,8 @@ __all__ = [
     "allreduce_scaled", "set_op_scaling", "Min", "Max", "allreduce_reduce_op",
     "sparse_allreduce", "set_sparse_reduce", "sparse_stats",
     "Adasum", "adasum_op", "fused_adasum_flat",
+    "MXFP8Compressor", "allreduce_mxfp8", "fused_allreduce_mxfp8", "mxfp8_quantize", "mxfp8_fold", "mxfp8_dequantize",
+    "mxfp8_wire_bytes",
 ]
 
 
@@ -67,6 +71,13 @@ def _op_scale(op, prescale_factor=1.0, postscale_factor=1.0):
     if op == Average:
         post = post / size()
     return None if (pre == 1.0 and post == 1.0) else (pre, post)
+
+
+def _no_mxfp8_op(compression, op):
+    """Compression.fp8 rides the sum only: Max, Min and Adasum with it raise before any collective."""
+    if compression is MXFP8Compressor and op in (Max, Min, Adasum):
+        raise ValueError("op=%s does not combine with Compression.fp8: the MXFP8 wire carries SUM (and Average) only"
+                         % op)
 
 
 def _no_integer_average(tensor, op):
@@ -119,7 +130,17 @@ def allreduce(tensor,
     for the sum (the tree then runs in the compressed dtype). It raises
     ValueError with a scale factor other than 1, a `name`, a sparse input, an
     integer dtype or a host tensor.
+
+    compression=Compression.fp8 sends a dense float32 device tensor through the
+    MXFP8 collective (ops.allreduce_mxfp8): e4m3fn bytes with one
+    power-of-two scale per 32 elements on the wire, the ranks' blocks folded in
+    rank order in f32 and requantised once. Under set_op_scaling(True) the
+    factors travel as one float32 factor prescale * postscale applied at the
+    dequantise. Every other tensor - host, another dtype, sparse, or a call with
+    a `name` - travels uncompressed, exactly as under Compression.none. op=Max,
+    Min or Adasum with it raises ValueError before any collective.
     """
+    _no_mxfp8_op(compression, op)
     if op in (Max, Min):
         return _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name)
     if op == Adasum:
@@ -140,6 +161,8 @@ def allreduce(tensor,
         return torch.sparse_coo_tensor(g_idx, g_vals, tensor.shape)
     _no_integer_average(tensor, op)
     scale = _op_scale(op, prescale_factor, postscale_factor)
+    if compression is MXFP8Compressor and name is None and _ops.is_mxfp8_tensor(tensor):
+        return allreduce_mxfp8(tensor, 1.0 if scale is None else scale[0] * scale[1])
     tensor_compressed, ctx = compression.compress(tensor)
     if scale is not None:
         summed_tensor_compressed = allreduce_scaled(tensor_compressed, scale[0], scale[1], name=name)
@@ -378,7 +401,15 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     Compression.fp16 each gradient is compressed, the list is reduced in
     float16 and each result decompressed - unfused casts, one launch per
     gradient each way. Host or sparse gradients raise ValueError.
+
+    Compression.fp8: the dense float32 device gradients go through the MXFP8
+    collective - per device one fused_allreduce_mxfp8 call with fused=True, one
+    allreduce_mxfp8 per gradient otherwise - with the factor prescale * postscale
+    under set_op_scaling(True); every other gradient (host, another dtype,
+    sparse) is reduced uncompressed, exactly as under Compression.none.
+    op=Max, Min or Adasum with it raises ValueError.
     """
+    _no_mxfp8_op(compression, op)
     _no_minmax_grads(op)
     if op == Adasum:
         if gradient_predivide_factor != 1.0:
@@ -438,6 +469,8 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
         outputs views of it (reused as the device flat outputs are);
       - the rest (sparse) one by one, through the reference's allgather branch."""
     _no_minmax_grads(op)
+    if compression is MXFP8Compressor:
+        return _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor)
     none = compression is Compression.none
     global _DATA_PTR
     if _DATA_PTR is None:
@@ -517,6 +550,34 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
             out[i] = s if none else compression.decompress(s, ctx)
     if simple:
         _remember_plan(grads, plan_groups)
+    return out
+
+
+def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor):
+    """_reduce_grads under Compression.fp8: the dense float32 device gradients through the MXFP8
+    collective (per device one fused_allreduce_mxfp8, or one allreduce_mxfp8 each with fused=False),
+    the factor prescale * postscale of set_op_scaling multiplied in double; the rest of the list as
+    under Compression.none."""
+    scale = _average_scale(op, gradient_predivide_factor)
+    factor = 1.0 if scale is None else scale[0] * scale[1]
+    out, rest, groups = list(grads), [], {}
+    for i, g in enumerate(grads):
+        if g is not None and _ops.is_mxfp8_tensor(g):
+            g = g if g.is_contiguous() else g.contiguous()
+            if fused:
+                groups.setdefault(g.device, []).append((i, g))
+            else:
+                out[i] = allreduce_mxfp8(g, factor)
+            rest.append(None)
+        else:
+            rest.append(g)
+    for members in groups.values():
+        for (i, _), s in zip(members, fused_allreduce_mxfp8([g for _, g in members], factor)):
+            out[i] = s
+    if any(g is not None for g in rest):
+        for i, g in enumerate(_reduce_grads(rest, Compression.none, op, fused, gradient_predivide_factor)):
+            if g is not None:
+                out[i] = g
     return out
 
 

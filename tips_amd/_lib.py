@@ -110,6 +110,16 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]),
     ("tips_fused_allreduce_adasum_flat", ctypes.c_int,
      [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tips_mxfp8_wire_bytes", ctypes.c_int64, [ctypes.c_int64, _c_i64_p]),
+    ("tips_mxfp8_quantize", ctypes.c_int, [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tips_mxfp8_fold", ctypes.c_int,
+     [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    ("tips_mxfp8_dequantize", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
+    ("tips_allreduce_mxfp8", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p]),
+    ("tips_fused_allreduce_mxfp8_flat", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

@@ -62,7 +62,24 @@ class FP16Compressor(Compressor):
         return np.asarray(tensor).astype(ctx)
 
 
+class MXFP8Compressor(Compressor):
+    """Block-scaled 8-bit wire. A marker, not a cast: an (8-bit payload, scales) pair
+    cannot pass through a sum allreduce, so compress / decompress are the identity, and allreduce /
+    allreduce_grads recognise the class and send float32 device tensors through the quantised
+    collective (ops.allreduce_mxfp8 / ops.fused_allreduce_mxfp8). Every other tensor - host, another
+    dtype, sparse - travels uncompressed, exactly as under Compression.none."""
+
+    @staticmethod
+    def compress(tensor):
+        return tensor, None
+
+    @staticmethod
+    def decompress(tensor, ctx):
+        return tensor
+
+
 class Compression(object):
     """Optional gradient compression algorithm used during allreduce (compression.py:69-75)."""
     none = NoneCompressor
     fp16 = FP16Compressor
+    fp8 = MXFP8Compressor

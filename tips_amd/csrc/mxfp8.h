@@ -1,0 +1,50 @@
+// mxfp8.h — the MXFP8 wire format's sizes and the launchers of its three kernels (mxfp8.hip;
+// DESIGN.md §16). Internal to libtips_hip.so (not part of the C-ABI).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace tips {
+
+// A block is 32 consecutive elements of the flat f32 layout (fused_layout: every tensor starts on a
+// multiple of 64 elements, so no block straddles two tensors). The wire buffer of E flat elements:
+// one payload byte per element from byte 0, one scale byte per block from byte round_up(E, 256).
+constexpr int kMxBlock = 32;
+inline int64_t mxfp8_blocks(int64_t elems) { return (elems + kMxBlock - 1) / kMxBlock; }
+inline int64_t mxfp8_scales_offset(int64_t elems) { return (elems + 255) / 256 * 256; }
+inline int64_t mxfp8_wire_bytes(int64_t elems) { return mxfp8_scales_offset(elems) + (mxfp8_blocks(elems) + 255) / 256 * 256; }
+
+// One tensor of a quantise / dequantise launch: `count` f32 elements at `ptr` (4-B aligned), which
+// lie at flat elements [off, off + count); the launch covers flat elements [off, off + span) (span a
+// multiple of 32: for the quantise the tensor and the padding behind it, which encodes as zeros; for
+// the dequantise the tensor's blocks). ptr == nullptr with count 0: padding only. Segments ascend.
+struct MxSeg {
+  const void* ptr;
+  int64_t off, count, span;
+};
+// Up to this many segments travel with one launch, by value (no table upload: a training step
+// brings new gradient pointers every time). Longer lists take several launches.
+constexpr int kMxSegsPerLaunch = 48;
+constexpr int64_t kMxTileElems = 4096;  // per workgroup: 256 lanes x 4 rounds x 4 elements
+
+// Quantise the segments into the wire buffer (payload, scales: 16-B aligned). `scale_tail`: the
+// scale bytes [scale_tail.first, scale_tail.second) are zeroed by the launch as well (the alignment
+// tail behind the last block; pass {0, 0} for none).
+hipError_t launch_mxfp8_quantize(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
+                                 int64_t tail_begin, int64_t tail_end, hipStream_t s);
+// dst = quantise(fold of the sources' blocks in order), over `nblocks` blocks: payload pointers at the
+// range's first block (16-B aligned), scale pointers at its first scale byte. dst may be a source.
+constexpr int kMxMaxSrcs = 16;
+struct MxSrcs {
+  const unsigned char* payload[kMxMaxSrcs];
+  const unsigned char* scales[kMxMaxSrcs];
+};
+hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
+                             int64_t nblocks, hipStream_t s);
+// Dequantise the segments' elements (segs[i].ptr: the f32 destination) from the wire buffer; factor
+// as an f32 multiply behind the decode when it is not 1.
+hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,
+                                   float factor, hipStream_t s);
+
+}  // namespace tips

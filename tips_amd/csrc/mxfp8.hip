@@ -1,0 +1,309 @@
+// mxfp8.hip — the MXFP8 wire: block-scaled 8-bit quantise, fold-requantise and dequantise.
+//
+// The operand is the flat f32 layout of a tensor list (fused_layout: tensors at 256-B aligned offsets).
+// A block is 32 consecutive flat elements; it never straddles two tensors; positions that hold no
+// tensor element count as +0. The wire buffer of E flat elements is E payload bytes (OCP e4m3fn, one
+// per element) from byte 0 and one scale byte per block from byte round_up(E, 256).
+//
+// Quantise, per block x_0 ... x_31:
+//   1. any NaN or +-Inf: the block is poisoned - scale byte 0xFF, all 32 payload bytes 0x7F.
+//   2. else amax = max |x_j| with biased exponent be and fraction fr: e = max(be, 1) - 127,
+//      s = e - 8 + (fr > 0x600000), clamped to [-127, 119], s = -127 for amax == 0; scale byte = s + 127.
+//   3. v_j = x_j * 2^-s (one f32 multiply), |v_j| clamped to 448, rounded to nearest even onto the
+//      e4m3fn grid, sign kept (-0 -> 0x80). amax * 2^-s <= 448 by the fr rule, so the clamp only binds
+//      for amax > 448 * 2^119.
+// Dequantise: y = decode(byte) * 2^(scale byte - 127), one IEEE f32 multiply for scale bytes 0 ... 254
+// (subnormals honoured, overflow to +-Inf), NaN for scale byte 255 or payload 0x7F / 0xFF; with a
+// factor other than 1 one more f32 multiply y * factor. Every NaN is stored as 0x7FC00000.
+// Fold of sources 0 ... k-1: each dequantised (factor 1), acc = ((y0 + y1) + y2) + ... as separate f32
+// adds, then quantised - a poisoned source block makes acc NaN, a sum that overflows makes it +-Inf,
+// and rule 1 poisons the result block.
+//
+// Which conversions are the hardware's (each compared with the integer restatement over every f32
+// input with |v| <= 448 resp. every code and scale byte on an MI355X: no difference):
+//   f32 -> e4m3fn, after the multiply and the clamp: v_cvt_pk_fp8_f32;
+//   e4m3fn -> f32 of the fold: v_cvt_pk_f32_fp8, then v_mul_f32 by the scale;
+//   e4m3fn -> f32 * 2^(scale - 127) of the dequantise: v_cvt_scalef32_pk_f32_fp8.
+// v_cvt_scalef32_pk_fp8_f32 is not used: it does not saturate (a quotient above 448 becomes 0x7F)
+// and its result under the scale 2^-127 differs from the definition.
+//
+// Launch shapes. Quantise and dequantise: one workgroup of 256 lanes per tile of 4096 flat elements
+// of one segment (tensor), 4 rounds of 4 elements per lane - a 16-B load (store) per lane and round
+// where the tensor's address is 16-B aligned and the 4 elements lie inside it, element by element
+// otherwise, into the same lanes: the same bits. 8 lanes make a block; its maximum takes three
+// cross-lane steps inside a row (DPP). Each lane stores its 4 payload bytes as one dword; the block's
+// first lane stores the scale byte. Fold: 16 payload bytes per lane and source, two lanes per block.
+#include "kernels_device.h"
+#include "mxfp8.h"
+
+namespace tips {
+
+namespace {
+
+constexpr int kMxRounds = 4;
+static_assert(kMxTileElems == (int64_t)kBlock * kMxRounds * 4, "a tile is 256 lanes x 4 rounds x 4 elements");
+constexpr unsigned kInfBits = 0x7f800000u, kQuietNaN = 0x7fc00000u, kMax448 = 0x43e00000u;
+
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+struct MxSegList {
+  MxSeg seg[kMxSegsPerLaunch];
+  int64_t tile0[kMxSegsPerLaunch + 1];  // the first tile of each segment among the launch's tiles
+  int nseg;
+};
+
+// max over the 8 lanes of a block (lanes 8k ... 8k + 7 of a row): xor 1, xor 2 inside the quad, then
+// the mirrored half row - after the first two steps every lane of a quad holds the quad's maximum
+__device__ __forceinline__ unsigned max8(unsigned v) {
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+  v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+  return v;
+}
+__device__ __forceinline__ unsigned max2(unsigned v) {
+  return max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));
+}
+
+// scale byte of a block whose largest |x| has the bits `am` (finite)
+__device__ __forceinline__ unsigned scale_byte(unsigned am) {
+  const int be = (int)(am >> 23);
+  int s = max(be, 1) - 127 - 8 + ((am & 0x7fffffu) > 0x600000u ? 1 : 0);
+  s = min(max(s, -127), 119);
+  return am == 0 ? 0u : (unsigned)(s + 127);
+}
+
+// x * 2^-s with |.| clamped to 448, s = sb - 127: the multiplier's biased exponent is 254 - sb (8 ... 254)
+__device__ __forceinline__ float scaled_clamped(float x, float mul) {
+#pragma clang fp contract(off)
+  const unsigned b = __builtin_bit_cast(unsigned, x * mul);
+  return __builtin_bit_cast(float, min(b & 0x7fffffffu, kMax448) | (b & 0x80000000u));
+}
+
+// 4 elements -> 4 payload bytes (element j in byte j)
+__device__ __forceinline__ unsigned encode4(f32x4 x, unsigned sb) {
+  const float mul = __builtin_bit_cast(float, (254u - sb) << 23);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(scaled_clamped(x[0], mul), scaled_clamped(x[1], mul), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(scaled_clamped(x[2], mul), scaled_clamped(x[3], mul), w, true);
+  return (unsigned)w;
+}
+
+__device__ __forceinline__ unsigned abs_max4(f32x4 x) {
+  const u32x4 b = __builtin_bit_cast(u32x4, x) & 0x7fffffffu;
+  return max(max(b[0], b[1]), max(b[2], b[3]));
+}
+
+// 2^(sb - 127) for sb 0 ... 254 (sb 0: the subnormal 2^-127), NaN for 255
+__device__ __forceinline__ float scale_value(unsigned sb) {
+  return __builtin_bit_cast(float, sb == 255u ? kQuietNaN : (sb ? (sb << 23) : 0x00400000u));
+}
+
+// the segment that tile t of the launch belongs to
+__device__ __forceinline__ int seg_of_tile(const MxSegList& L, int64_t t) {
+  int lo = 0, hi = L.nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (L.tile0[mid] <= t) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void mxfp8_quantize_kernel(MxSegList L, unsigned char* __restrict__ payload,
+                                                                unsigned char* __restrict__ scales, int64_t tail_begin,
+                                                                int64_t tail_end) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0)  // the scale bytes behind the last block, up to the buffer's end
+    for (int64_t j = tail_begin + tid; j < tail_end; j += kBlock) scales[j] = 0;
+  const int64_t t = blockIdx.x;
+  const int si = seg_of_tile(L, t);
+  const MxSeg sg = L.seg[si];
+  const int64_t base = (t - L.tile0[si]) * kMxTileElems;
+  const float* src = (const float*)sg.ptr;
+  const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+  f32x4 x[kMxRounds];
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (vec && i0 + 4 <= sg.count) {
+      x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
+    } else if (i0 < sg.count) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) x[u][j] = src[i0 + j];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    const unsigned am = max8(abs_max4(x[u]));  // (every lane takes part: lanes past the span hold zeros)
+    if (i0 >= sg.span) continue;
+    const bool poisoned = am >= kInfBits;
+    const unsigned sb = poisoned ? 255u : scale_byte(am);
+    const unsigned w = poisoned ? 0x7f7f7f7fu : encode4(x[u], sb);
+    *(unsigned*)(payload + sg.off + i0) = w;
+    if ((tid & 7) == 0) scales[(sg.off + i0) >> 5] = (unsigned char)sb;
+  }
+}
+
+// two payload bytes of a word -> f32 (the hardware's decode), times the block's scale
+template <bool HI>
+__device__ __forceinline__ f32x2 decode2(unsigned w, float scale) {
+#pragma clang fp contract(off)
+  return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI) * scale;
+}
+
+__global__ __launch_bounds__(kBlock) void mxfp8_fold_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
+                                                            MxSrcs srcs, int nsrc, int64_t nblocks) {
+#pragma clang fp contract(off)
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // 16 elements each: two lanes per block
+  const int64_t blk = g >> 1;
+  const bool active = blk < nblocks;
+  float acc[16];
+#pragma unroll
+  for (int j = 0; j < 16; j++) acc[j] = 0.f;
+  if (active) {
+    u32x4 v = ld16<true>((const u32x4*)srcs.payload[0] + g);
+    unsigned sb = srcs.scales[0][blk];
+    for (int k = 0; k < nsrc; k++) {
+      const u32x4 cur = v;
+      const float scale = scale_value(sb);
+      if (k + 1 < nsrc) {  // the next source's bytes are on their way while this one is decoded
+        v = ld16<true>((const u32x4*)srcs.payload[k + 1] + g);
+        sb = srcs.scales[k + 1][blk];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const f32x2 lo = decode2<false>(cur[q], scale), hi = decode2<true>(cur[q], scale);
+        if (k == 0) {
+          acc[4 * q] = lo[0], acc[4 * q + 1] = lo[1], acc[4 * q + 2] = hi[0], acc[4 * q + 3] = hi[1];
+        } else {
+          acc[4 * q] = acc[4 * q] + lo[0];
+          acc[4 * q + 1] = acc[4 * q + 1] + lo[1];
+          acc[4 * q + 2] = acc[4 * q + 2] + hi[0];
+          acc[4 * q + 3] = acc[4 * q + 3] + hi[1];
+        }
+      }
+    }
+  }
+  unsigned am = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) am = max(am, __builtin_bit_cast(unsigned, acc[j]) & 0x7fffffffu);
+  am = max2(am);
+  if (!active) return;
+  const bool poisoned = am >= kInfBits;
+  const unsigned sb = poisoned ? 255u : scale_byte(am);
+  u32x4 w;
+#pragma unroll
+  for (int q = 0; q < 4; q++)
+    w[q] = poisoned ? 0x7f7f7f7fu : encode4(f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]}, sb);
+  st16<false>((u32x4*)dst_payload + g, w);
+  if ((g & 1) == 0) dst_scales[blk] = (unsigned char)sb;
+}
+
+__device__ __forceinline__ float canonical(float y) {
+  return y != y ? __builtin_bit_cast(float, kQuietNaN) : y;
+}
+
+__global__ __launch_bounds__(kBlock) void mxfp8_dequantize_kernel(MxSegList L, const unsigned char* __restrict__ payload,
+                                                                  const unsigned char* __restrict__ scales, float factor,
+                                                                  int has_factor) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  const int64_t t = blockIdx.x;
+  const int si = seg_of_tile(L, t);
+  const MxSeg sg = L.seg[si];
+  const int64_t base = (t - L.tile0[si]) * kMxTileElems;
+  float* dst = (float*)const_cast<void*>(sg.ptr);
+  const bool vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  unsigned w[kMxRounds], sb[kMxRounds];
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    w[u] = 0, sb[u] = 0;
+    if (i0 < sg.count) {
+      w[u] = *(const unsigned*)(payload + sg.off + i0);
+      sb[u] = scales[(sg.off + i0) >> 5];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    if (i0 >= sg.count) continue;
+    const float scale = scale_value(sb[u]);
+    const f32x2 lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((int)w[u], scale, false);
+    const f32x2 hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((int)w[u], scale, true);
+    f32x4 y = {lo[0], lo[1], hi[0], hi[1]};
+    if (has_factor) y = y * factor;
+#pragma unroll
+    for (int j = 0; j < 4; j++) y[j] = canonical(y[j]);
+    if (vec && i0 + 4 <= sg.count) {
+      st16<false>((u32x4*)(dst + i0), __builtin_bit_cast(u32x4, y));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) dst[i0 + j] = y[j];
+    }
+  }
+}
+
+// the launches of a segment list, kMxSegsPerLaunch segments at a time; launch(list, tiles) per part
+template <class F>
+hipError_t for_each_part(const MxSeg* segs, int nseg, bool by_span, F launch) {
+  for (int first = 0; first < nseg; first += kMxSegsPerLaunch) {
+    MxSegList L;
+    L.nseg = 0;
+    int64_t tiles = 0;
+    for (int i = first; i < nseg && i < first + kMxSegsPerLaunch; i++) {
+      const int64_t cover = by_span ? segs[i].span : segs[i].count;
+      if (cover <= 0) continue;
+      L.seg[L.nseg] = segs[i];
+      L.tile0[L.nseg++] = tiles;
+      tiles += (cover + kMxTileElems - 1) / kMxTileElems;
+    }
+    if (!L.nseg) continue;
+    L.tile0[L.nseg] = tiles;
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    const hipError_t err = launch(L, (unsigned)tiles);
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_mxfp8_quantize(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
+                                 int64_t tail_begin, int64_t tail_end, hipStream_t s) {
+  if (!segs || nseg < 1 || !payload || !scales) return hipErrorInvalidValue;
+  bool first = true;
+  return for_each_part(segs, nseg, true, [&](const MxSegList& L, unsigned tiles) {
+    hipLaunchKernelGGL(mxfp8_quantize_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales,
+                       first ? tail_begin : (int64_t)0, first ? tail_end : (int64_t)0);
+    first = false;
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
+                             int64_t nblocks, hipStream_t s) {
+  if (!dst_payload || !dst_scales || nsrc < 1 || nsrc > kMxMaxSrcs || nblocks < 0) return hipErrorInvalidValue;
+  if (nblocks == 0) return hipSuccess;
+  const int64_t grid = (2 * nblocks + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mxfp8_fold_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
+                     nblocks);
+  return hipGetLastError();
+}
+
+hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,
+                                   float factor, hipStream_t s) {
+  if (!segs || nseg < 1 || !payload || !scales) return hipErrorInvalidValue;
+  return for_each_part(segs, nseg, false, [&](const MxSegList& L, unsigned tiles) {
+    hipLaunchKernelGGL(mxfp8_dequantize_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales, factor,
+                       factor != 1.0f ? 1 : 0);
+    return hipGetLastError();
+  });
+}
+
+}  // namespace tips

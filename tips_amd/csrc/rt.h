@@ -219,6 +219,12 @@ struct State {
   std::mutex adasum_mu;
   hipEvent_t ev_adasum = nullptr;
   bool adasum_chain_valid = false;
+  // mxfp8.cc, the MXFP8 collectives: this rank's wire buffer, the reduced wire buffer and the peers'
+  // staged chunks. One call at a time (mxfp8_mu), chained across calling streams like the Adasum scratch.
+  DevBuf mxfp8_scratch;
+  std::mutex mxfp8_mu;
+  hipEvent_t ev_mxfp8 = nullptr;
+  bool mxfp8_chain_valid = false;
   void* bounce_in = nullptr;  // page-locked kBounceBytes each (hipHostMalloc), for small pageable host tensors
   void* bounce_out = nullptr;
   HostPool* host_pool = nullptr;  // fused host tensors: pack / unpack threads
@@ -367,6 +373,7 @@ bool on_negotiation_thread();
 bool negotiation_running();
 void sparse_release(State& st);  // sparse.cc (shutdown)
 void adasum_release(State& st);  // adasum.cc (shutdown: the scratch and the cached segment tables)
+void mxfp8_release(State& st);   // mxfp8.cc (shutdown: the scratch)
 // fusion.cc: the flat call's pack alone - every tensor of the list copied to its fused_layout offset
 // in `flat` (items[i].out = flat), one launch, in the fusion chain. Caller holds st.mu.
 int fused_pack_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t stream);

@@ -131,6 +131,7 @@ void tips_shutdown(void) {
   st.cast_scratch.release();
   sparse_release(st);
   adasum_release(st);
+  mxfp8_release(st);
   st.tuned.clear();
   st.recv_ev.release();
   st.sum_ev.release();

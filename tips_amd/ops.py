@@ -631,6 +631,109 @@ def fused_adasum_flat(tensor_list):
     return views
 
 
+def is_mxfp8_tensor(t):
+    """A tensor the MXFP8 collectives take: a dense float32 device tensor."""
+    return tensors.is_torch(t) and t.is_cuda and not t.is_sparse and t.dtype == _torch_mod().float32
+
+
+def _check_mxfp8_list(tensor_list, what):
+    for t in tensor_list:
+        if not is_mxfp8_tensor(t):
+            raise ValueError("%s takes dense float32 device tensors only" % what)
+        if not t.is_contiguous():
+            raise ValueError("%s needs contiguous tensors" % what)
+
+
+def mxfp8_wire_bytes(flat_elems):
+    """(bytes of the MXFP8 wire buffer of `flat_elems` flat elements, offset of its scale bytes):
+    round_up(E, 256) + round_up(E / 32, 256) and round_up(E, 256) (tips_mxfp8_wire_bytes; pure host)."""
+    import ctypes
+    so = ctypes.c_int64()
+    return int(_lib.call("tips_mxfp8_wire_bytes", int(flat_elems), ctypes.byref(so))), int(so.value)
+
+
+def mxfp8_flat_elems(counts):
+    """Flat elements of the list's layout (tips_fused_layout bytes / 4) and the tensors' element offsets."""
+    import ctypes
+    cp, _keep = _lib.i64_array(counts)
+    offs = (ctypes.c_int64 * max(1, len(counts)))()
+    total = _lib.check("tips_fused_layout", _lib.lib().tips_fused_layout(cp, len(counts), _lib.FLOAT32, offs))
+    return total // 4, [int(o) // 4 for o in offs[:len(counts)]]
+
+
+def mxfp8_quantize(tensor_list, wire=None):
+    """The MXFP8 wire buffer (a uint8 device tensor) of a list of float32 device tensors
+    (tips_mxfp8_quantize): one e4m3fn byte per flat element, one power-of-two scale byte per block of
+    32; every byte of the buffer is written. `wire`: a 16-B aligned uint8 tensor to fill."""
+    import torch
+    _check_mxfp8_list(tensor_list, "mxfp8_quantize")
+    counts = [t.numel() for t in tensor_list]
+    elems, _ = mxfp8_flat_elems(counts)
+    nbytes, _ = mxfp8_wire_bytes(elems)
+    if wire is None:
+        wire = torch.empty(nbytes, dtype=torch.uint8, device=tensor_list[0].device if tensor_list else "cuda")
+    if tensor_list:
+        pp, _k1 = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+        cp, _k2 = _lib.i64_array(counts)
+        _lib.call("tips_mxfp8_quantize", pp, cp, len(counts), wire.data_ptr(), tensors.stream_of(tensor_list[0]))
+    return wire
+
+
+def mxfp8_fold(dst_wire, src_wires, flat_elems, block_begin, block_count):
+    """Blocks [block_begin, block_begin + block_count) of dst_wire = quantise(((y0 + y1) + y2) + ...)
+    of the sources' dequantised blocks, in source order (tips_mxfp8_fold); dst_wire may be a source."""
+    pp, _k1 = _lib.ptr_array([w.data_ptr() for w in src_wires])
+    _lib.call("tips_mxfp8_fold", dst_wire.data_ptr(), pp, len(src_wires), int(flat_elems), int(block_begin),
+              int(block_count), tensors.stream_of(dst_wire))
+    return dst_wire
+
+
+def mxfp8_dequantize(wire, out_list, factor=1.0):
+    """Fill the float32 device tensors of `out_list` from their list's wire buffer
+    (tips_mxfp8_dequantize): decode * 2^(scale - 127), then * float32(factor) when factor != 1."""
+    _check_mxfp8_list(out_list, "mxfp8_dequantize")
+    if out_list:
+        pp, _k1 = _lib.ptr_array([t.data_ptr() for t in out_list])
+        cp, _k2 = _lib.i64_array([t.numel() for t in out_list])
+        _lib.call("tips_mxfp8_dequantize", pp, cp, len(out_list), wire.data_ptr(), float(factor), tensors.stream_of(wire))
+    return out_list
+
+
+def allreduce_mxfp8(tensor, factor=1.0):
+    """factor * SUM of `tensor` over all ranks with an MXFP8 wire, out of place (tips_allreduce_mxfp8;
+    DESIGN.md §16): every rank's tensor is quantised once to e4m3fn bytes with one power-of-two scale
+    per 32 elements, rank q folds chunk q of all ranks in rank order in f32 and requantises it once,
+    the reduced chunks are gathered and dequantised - a quarter of the float32 bytes on the links,
+    the same bits on every rank and every run; one rank returns the round trip. A dense float32
+    device tensor; the same factor on every rank; stream-ordered."""
+    if not is_mxfp8_tensor(tensor):
+        raise ValueError("allreduce_mxfp8 takes a dense float32 device tensor")
+    basics.init()
+    src = tensors.contiguous(tensor)
+    out = tensors.empty_like(src)
+    n = tensors.numel(src)
+    if n:
+        _lib.call("tips_allreduce_mxfp8", tensors.data_ptr(src), tensors.data_ptr(out), n, float(factor),
+                  tensors.stream_of(src))
+    return out
+
+
+def fused_allreduce_mxfp8(tensor_list, factor=1.0):
+    """allreduce_mxfp8 of a list of float32 device tensors in one call
+    (tips_fused_allreduce_mxfp8_flat): the outputs are views of one flat float32 buffer laid out and
+    reused as fused_allreduce_flat's. Inputs unchanged."""
+    if not tensor_list:
+        return []
+    _check_mxfp8_list(tensor_list, "fused_allreduce_mxfp8")
+    basics.init()
+    fo = _flat_outputs(tensor_list, _lib.FLOAT32)
+    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+    flat, views = fo.take()
+    _lib.call("tips_fused_allreduce_mxfp8_flat", pp[0], fo.cp[0], len(tensor_list), flat.data_ptr(), float(factor),
+              _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+    return views
+
+
 def _flat_call(tensor_list, code, ptrs, scale=None):
     return _flat_run(_flat_outputs(tensor_list, code), tensor_list, ptrs, scale)
 
