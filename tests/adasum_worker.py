@@ -72,6 +72,15 @@ def main():
             res["ok"] = rc == -7 and "Mismatched Adasum" in _lib.last_error() and sum_still_works()
             results.append(res)
             continue
+        if kind == "refused":  # rank 1's `in` is host memory: its own error there, "refused" on the others, nobody waits
+            t = dev(vals[rank], dtype)
+            out = torch.empty_like(t)
+            rc = L.tips_allreduce_adasum(vals[rank].ctypes.data if rank == 1 else t.data_ptr(), out.data_ptr(), n, dtype, sp)
+            res.update(rc=int(rc), error=_lib.last_error())
+            want = (-5, "host memory") if rank == 1 else (-7, "refused its arguments")
+            res["ok"] = rc == want[0] and want[1] in res["error"] and sum_still_works()
+            results.append(res)
+            continue
         if not pow2:  # refused on every rank before any exchange; the job goes on
             t = dev(vals[rank], dtype)
             out = torch.empty_like(t)

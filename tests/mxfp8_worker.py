@@ -70,6 +70,16 @@ def main():
             res["ok"] = rc == -7 and "Mismatched MXFP8" in _lib.last_error() and sum_still_works()
             results.append(res)
             continue
+        if kind == "refused":  # rank 1's input is host memory: its own error there, "refused" on the others, nobody waits
+            a = np.ascontiguousarray(vals[rank])
+            t = dev(a)
+            out = torch.empty_like(t)
+            rc = L.tips_allreduce_mxfp8(a.ctypes.data if rank == 1 else t.data_ptr(), out.data_ptr(), n, 1.0, sp)
+            res.update(rc=int(rc), error=_lib.last_error())
+            want = (-5, "host memory") if rank == 1 else (-7, "refused its arguments")
+            res["ok"] = rc == want[0] and want[1] in res["error"] and sum_still_works()
+            results.append(res)
+            continue
         elems, offs = ops.mxfp8_flat_elems(counts)
         if kind == "mixed":  # f32 device, bf16 device and host numpy members in one list
             f32s = split(vals[rank], counts)

@@ -3,7 +3,7 @@
 Run as: python sparse_worker.py RANK SIZE CASES_JSON, with the RCCL environment of
 tests/test_gpu_rccl_procs.py (rccl_env): every process is its own RCCL rank on the one GPU, named as
 its own host (NCCL_HOSTID) so RCCL joins them over its socket transport. Each case is run through
-tips_amd.sparse_allreduce (or, for the mismatch case, tips_sparse_allreduce itself) and compared bit
+tips_amd.sparse_allreduce (or, for the mismatch and refused cases, tips_sparse_allreduce itself) and compared bit
 for bit with tests/sparse_util.py on the concatenation of every rank's entries in rank order - every
 rank generates all ranks' inputs from the case's seed. Prints one JSON line: {"rank", "results"}.
 """
@@ -52,6 +52,13 @@ def main():
     assert tips_amd.size() == size and tips_amd.rank() == rank
     L = _lib.lib()
     sp = torch.cuda.current_stream().cuda_stream
+
+    def sum_still_works():
+        t = torch.full((1000,), float(rank + 1), device="cuda")
+        out = tips_amd.allreduce(t)
+        torch.cuda.synchronize()
+        return bool(torch.all(out == size * (size + 1) / 2).item())
+
     results = []
     for c in cases:
         dtype, rows, D = c["dtype"], c["rows"], c["D"]
@@ -65,7 +72,18 @@ def main():
             out = torch.empty(rows * d, dtype=tv.dtype, device="cuda")
             rc = L.tips_sparse_allreduce(tv.data_ptr(), ti.data_ptr(), len(idx) if rank != 1 else 0, rows, d, dtype, 1.0, 1.0,
                                          out.data_ptr(), sp)
-            res.update(rc=int(rc), error=_lib.last_error(), ok=rc == -7 and "Mismatched sparse allreduce" in _lib.last_error())
+            res.update(rc=int(rc), error=_lib.last_error())
+            res["ok"] = rc == -7 and "Mismatched sparse allreduce" in res["error"] and sum_still_works()
+            results.append(res)
+            continue
+        if c.get("refused"):  # rank 1's dense_out is host memory: its own error there, "refused" on the others, nobody waits
+            host_out = np.empty(rows * D, values.dtype)
+            out = torch.empty(rows * D, dtype=tv.dtype, device="cuda")
+            rc = L.tips_sparse_allreduce(tv.data_ptr(), ti.data_ptr(), len(idx), rows, D, dtype, 1.0, 1.0,
+                                         host_out.ctypes.data if rank == 1 else out.data_ptr(), sp)
+            res.update(rc=int(rc), error=_lib.last_error())
+            want = (-5, "host memory") if rank == 1 else (-7, "refused its arguments")
+            res["ok"] = rc == want[0] and want[1] in res["error"] and sum_still_works()
             results.append(res)
             continue
         if dtype == BF16:

@@ -6,7 +6,9 @@ config-like list of 20 tensors with a 1-element and an empty one, f32 and bf16 -
 bit the restatement's tree (tests/adasum_util.py), one sha1 across the ranks. p = 2 also through
 allreduce(op=Adasum) and allreduce_grads(op=Adasum), fused and not. p = 3: TIPS_ERR_UNSUPPORTED on
 every rank, and a SUM allreduce afterwards still works. A rank with another count list:
-TIPS_ERR_MISMATCH on every rank, and the job goes on."""
+TIPS_ERR_MISMATCH on every rank, and the job goes on. A rank whose input is host memory: its own
+TIPS_ERR_UNSUPPORTED there, TIPS_ERR_MISMATCH ("refused its arguments") on every other rank, nobody
+waits in the exchange, and the job goes on."""
 import json
 import os
 import signal
@@ -72,6 +74,7 @@ def adasum_cases(p):
         cases.append({"kind": "grads", "dtype": F32, "counts": LIST20[:8], "seed": 43})
         cases.append({"kind": "grads_unfused", "dtype": BF16, "counts": [5, 300, 4099], "seed": 44})
     cases.append({"kind": "mismatch", "dtype": F32, "counts": [40, 50, 60], "seed": 50})
+    cases.append({"kind": "refused", "dtype": F32, "counts": [300], "seed": 52})
     cases.append({"kind": "single", "dtype": F32, "counts": [1], "seed": 51})  # the job goes on
     return cases
 
@@ -84,6 +87,10 @@ def check(results, p, cases):
         per_rank = [res["results"][i] for res in results]
         if "sha1" in per_rank[0]:
             assert len({r["sha1"] for r in per_rank}) == 1, (c, per_rank)
+        if c["kind"] == "refused":  # rank 1 refused its own `in`; the others hear of it
+            assert [r["rc"] for r in per_rank] == [-5 if k == 1 else -7 for k in range(p)], per_rank
+            assert "host memory" in per_rank[1]["error"], per_rank
+            assert all("refused its arguments" in r["error"] for k, r in enumerate(per_rank) if k != 1), per_rank
 
 
 @pytest.mark.parametrize("p", [2, 4, 8])

@@ -4,7 +4,9 @@ environment of tests/test_gpu_rccl_procs.py; at most 8 processes).
 p = 2, 3, 4, 8: tips_allreduce_mxfp8 over 1, 4099 and 70001 elements (out of place and in place, one
 with the factor 1 / p) and the flat list call over the 20-tensor list of the Adasum process test -
 every rank bit for bit the restatement's collective (tests/mxfp8_util.py), one sha1 across the ranks.
-A rank with another count list: TIPS_ERR_MISMATCH on every rank, and the job goes on. p = 2 also
+A rank with another count list: TIPS_ERR_MISMATCH on every rank, and the job goes on. A rank whose
+input is host memory: its own TIPS_ERR_UNSUPPORTED there, TIPS_ERR_MISMATCH ("refused its
+arguments") on every other rank, nobody waits in the exchange, and the job goes on. p = 2 also
 through allreduce(compression=Compression.fp8) and allreduce_grads(compression=Compression.fp8) -
 fused, unfused, op=Average under set_op_scaling(True), and a mixed list whose members that are not
 float32 device tensors equal the Compression.none result."""
@@ -79,6 +81,7 @@ def mxfp8_cases(p):
         cases.append({"kind": "grads_avg", "counts": [65, 1000, 4099, 3], "seed": 45})
         cases.append({"kind": "mixed", "counts": [300, 129, 77, 4099], "seed": 46})
     cases.append({"kind": "mismatch", "counts": [40, 50, 60], "seed": 50})
+    cases.append({"kind": "refused", "counts": [300], "seed": 52})
     cases.append({"kind": "single", "counts": [300], "seed": 51})  # the job goes on
     return cases
 
@@ -93,6 +96,10 @@ def check(results, p, cases):
             assert len({r["sha1"] for r in per_rank}) == 1, (c, per_rank)
         if c["kind"] == "mismatch":
             assert all(r["rc"] == -7 for r in per_rank), per_rank
+        if c["kind"] == "refused":  # rank 1 refused its own input; the others hear of it
+            assert [r["rc"] for r in per_rank] == [-5 if k == 1 else -7 for k in range(p)], per_rank
+            assert "host memory" in per_rank[1]["error"], per_rank
+            assert all("refused its arguments" in r["error"] for k, r in enumerate(per_rank) if k != 1), per_rank
 
 
 @pytest.mark.parametrize("p", [2, 3, 4, 8])

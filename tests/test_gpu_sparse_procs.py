@@ -6,7 +6,9 @@ Every rank brings a different number of entries, one rank none at all; index set
 bf16 and i64; op=Average with a predivision factor. Every rank must return the bits of
 tests/sparse_util.py on the concatenation of the ranks' entries in rank order, and therefore the
 bits of every other rank. A rank whose rows have another length makes every rank's call fail with
-TIPS_ERR_MISMATCH before any entries are exchanged, and the job carries on."""
+TIPS_ERR_MISMATCH before any entries are exchanged, and the job carries on. A rank whose dense_out
+is host memory gets its own TIPS_ERR_UNSUPPORTED, every other rank TIPS_ERR_MISMATCH ("refused its
+arguments"), nobody waits in the exchange, and a SUM allreduce afterwards still works."""
 import json
 import os
 import signal
@@ -71,6 +73,7 @@ def sparse_cases(p):
                   "predivide": 1.0})
     cases.append({"dtype": F32, "D": 4, "rows": 16, "ns": [0] * p, "sets": "overlap", "seed": 93})  # nobody has entries
     cases.append({"dtype": F32, "D": 6, "rows": 32, "ns": ns[2], "sets": "overlap", "seed": 94, "mismatch": True})
+    cases.append({"dtype": F32, "D": 16, "rows": 8, "ns": [4] * p, "sets": "overlap", "seed": 96, "refused": True})
     cases.append({"dtype": F32, "D": 6, "rows": 32, "ns": ns[2], "sets": "overlap", "seed": 95})  # the job goes on
     return cases
 
@@ -86,6 +89,10 @@ def test_sparse_allreduce_across_processes(gpu, p):
         per_rank = [res["results"][i] for res in results]
         if c.get("mismatch"):
             assert all(r["rc"] == -7 for r in per_rank), per_rank
+        elif c.get("refused"):  # rank 1 refused its own dense_out; the others hear of it
+            assert [r["rc"] for r in per_rank] == [-5 if k == 1 else -7 for k in range(p)], per_rank
+            assert "host memory" in per_rank[1]["error"], per_rank
+            assert all("refused its arguments" in r["error"] for k, r in enumerate(per_rank) if k != 1), per_rank
         else:
             assert len({r["sha1"] for r in per_rank}) == 1, (c, per_rank)
             assert per_rank[0]["entries"] == sum(c["ns"])

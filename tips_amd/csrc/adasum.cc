@@ -6,11 +6,11 @@
 // reference's allreduce names and never calls ("# TODO: Need to fix this to actuall call Adasum",
 // tips/tensorflow/__init__.py:62).
 #include <algorithm>
-#include <string>
 #include <vector>
 
 #include "adasum.h"
 #include "rt.h"
+#include "side.h"
 
 using namespace tips::rt;
 
@@ -27,12 +27,7 @@ int check_float(int dtype, const char* what) {
   return 0;
 }
 
-int need_device(const void* p, const char* what) {
-  if (!p) return fail(TIPS_ERR_INVALID_ARG, "null pointer (%s)", what);
-  if (!is_device_ptr(p))
-    return fail(TIPS_ERR_UNSUPPORTED, "%s is host memory: Adasum takes device pointers only (nothing is staged)", what);
-  return 0;
-}
+const char kTakes[] = "Adasum takes";  // need_device's phrase
 
 // ---------------------------------------------------------------------------
 // Segment tables: {offset, count, first chunk} per segment, uploaded once per layout (device, chunk
@@ -105,80 +100,43 @@ int find_segs(const int64_t* offs, const int64_t* counts, int nseg, int dtype, t
   return 0;
 }
 
-// the counts of a list: none negative, the total in *total
-int check_counts(const int64_t* counts, int n, int64_t* total) {
-  if (n < 0 || (n > 0 && !counts)) return fail(TIPS_ERR_INVALID_ARG, "bad segment list (n %d)", n);
-  *total = 0;
-  for (int i = 0; i < n; i++) {
-    if (counts[i] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count (segment %d: %lld)", i, (long long)counts[i]);
-    if (__builtin_add_overflow(*total, counts[i], total) || *total > ((int64_t)1 << 56))
-      return fail(TIPS_ERR_INVALID_ARG, "sizes overflow (segment %d)", i);
-  }
+int power_of_two(const char* what, int size) {
+  if ((size & (size - 1)) != 0)
+    return fail(TIPS_ERR_UNSUPPORTED, "%s needs a power-of-two number of ranks (recursive doubling), not %d", what, size);
   return 0;
 }
 
-uint64_t hash_counts(const int64_t* counts, int n) {  // FNV-1a over the counts' bytes
-  uint64_t h = 1469598103934665603ull;
-  for (int i = 0; i < n; i++)
-    for (int k = 0; k < 8; k++) h = (h ^ (((uint64_t)counts[i] >> (8 * k)) & 0xff)) * 1099511628211ull;
-  return h;
-}
-
-const char kBusy[] =
-    "%s does not go through a running negotiation (named Adasum requests are not implemented): call it before the "
-    "first named request or after tips_shutdown / tips_init";
-
-// What both collectives check before any device exchange: the lifecycle, the rank count, the
-// algorithm, and that every rank brings the same list and accepts its own pointers (`own`: this
-// rank's verdict, which travels with the record so that no rank is left waiting in the exchange).
-int agree(State& st, const char* what, int n, int64_t total, int dtype, const int64_t* counts, int own, int* size) {
-  const std::string own_msg = own ? last_error() : std::string();
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-    TRY(set_device(st));
-    *size = st.size;
-    if ((st.size & (st.size - 1)) != 0)
-      return fail(TIPS_ERR_UNSUPPORTED, "%s needs a power-of-two number of ranks (recursive doubling), not %d", what, st.size);
-    if (st.size > 1 && resolve_algo(st.algo, st.size, 0) == TIPS_ALGO_PEER)
-      return fail(TIPS_ERR_UNSUPPORTED, "%s has one schedule, over RCCL send / recv: not available under TIPS_ALGO_PEER", what);
+// What both collectives check once open (side_open), before any device exchange: that every rank
+// brings the same list and accepts its own pointers (`own`: this rank's verdict)
+int agree(int size, int n, int64_t total, int dtype, const int64_t* counts, int own) {
+  const int64_t mine[5] = {n, total, dtype, (int64_t)hash_counts(counts, n), own};
+  SideRecords rec;
+  TRY(side_exchange(size, mine, 5, &rec));
+  // reported in this order: a mismatch, another rank's refusal, this rank's own
+  if (const int r = rec.first_differing(0, 4); r >= 0) {
+    const int64_t *q = rec.of(r), *q0 = rec.of(0);
+    return fail(TIPS_ERR_MISMATCH,
+                "Mismatched Adasum allreduce: rank %d has %lld tensors, %lld elements, dtype %lld, count hash %llx; rank "
+                "0 has %lld tensors, %lld elements, dtype %lld, count hash %llx",
+                r, (long long)q[0], (long long)q[1], (long long)q[2], (unsigned long long)q[3], (long long)q0[0],
+                (long long)q0[1], (long long)q0[2], (unsigned long long)q0[3]);
   }
-  if (*size > 1) {
-    const int64_t mine[5] = {n, total, dtype, (int64_t)hash_counts(counts, n), own};
-    std::vector<int64_t> all((size_t)5 * *size);
-    TRY(tips_allgather_i64(mine, 5, all.data()));
-    for (int r = 0; r < *size; r++) {
-      const int64_t* q = &all[(size_t)5 * r];
-      if (q[0] != all[0] || q[1] != all[1] || q[2] != all[2] || q[3] != all[3])
-        return fail(TIPS_ERR_MISMATCH,
-                    "Mismatched Adasum allreduce: rank %d has %lld tensors, %lld elements, dtype %lld, count hash %llx; rank "
-                    "0 has %lld tensors, %lld elements, dtype %lld, count hash %llx",
-                    r, (long long)q[0], (long long)q[1], (long long)q[2], (unsigned long long)q[3], (long long)all[0],
-                    (long long)all[1], (long long)all[2], (unsigned long long)all[3]);
-    }
-    for (int r = 0; r < *size; r++)
-      if (all[(size_t)5 * r + 4] != 0 && !own)
-        return fail(TIPS_ERR_MISMATCH, "Adasum allreduce: rank %d refused its arguments (status %lld)", r,
-                    (long long)all[(size_t)5 * r + 4]);
-  }
-  if (own) return fail(own, "%s", own_msg.c_str());
-  return 0;
+  if (!own) TRY(rec.report_refusing("Adasum"));
+  return rec.report_own();
 }
 
 // The levels. `buf` holds this rank's value in its first span_bytes (segments at offs / counts,
 // elements) and receives the result; `first` is what level 0 reads as this rank's value (the input
-// of an out-of-place call, or buf). Caller holds st.mu and st.adasum_mu; size a power of two > 1.
+// of an out-of-place call, or buf). Caller holds st.mu and st.adasum.mu; size a power of two > 1.
 int run_levels(State& st, const void* first, void* buf, int64_t span_bytes, const int64_t* offs, const int64_t* counts,
                int nseg, int64_t total, int dtype, hipStream_t s) {
   tips::AdaSegs segs;
   int64_t nchunks;
   TRY(find_segs(offs, counts, nseg, dtype, &segs, &nchunks));
   const int64_t recv_bytes = round_up(span_bytes, kAlignBytes);
-  TRY(st.adasum_scratch.ensure((size_t)(recv_bytes + tips::adasum_workspace_bytes(total, nseg))));
-  char* recv = (char*)st.adasum_scratch.p;
+  TRY(st.adasum.open(s, (size_t)(recv_bytes + tips::adasum_workspace_bytes(total, nseg))));
+  char* recv = (char*)st.adasum.scratch.p;
   void* ws = recv + recv_bytes;
-  if (!st.ev_adasum) HIP_TRY(hipEventCreateWithFlags(&st.ev_adasum, hipEventDisableTiming));
-  if (st.adasum_chain_valid) HIP_TRY(hipStreamWaitEvent(s, st.ev_adasum, 0));
   TRY(ensure_comm(st));
   const void* mine = first;
   for (int bit = 1; bit < st.size; bit <<= 1) {
@@ -194,9 +152,7 @@ int run_levels(State& st, const void* first, void* buf, int64_t span_bytes, cons
     HIP_TRY(tips::launch_adasum_pair(buf, low ? mine : recv, low ? recv : mine, segs, nchunks, dtype, ws, s));
     mine = buf;
   }
-  HIP_TRY(hipEventRecord(st.ev_adasum, s));
-  st.adasum_chain_valid = true;
-  return 0;
+  return st.adasum.close(s);
 }
 
 }  // namespace
@@ -205,12 +161,7 @@ namespace tips {
 namespace rt {
 
 void adasum_release(State& st) {
-  st.adasum_scratch.release();
-  if (st.ev_adasum) {
-    (void)hipEventDestroy(st.ev_adasum);
-    st.ev_adasum = nullptr;
-  }
-  st.adasum_chain_valid = false;
+  st.adasum.release();
   std::lock_guard<std::mutex> lk(g_seg_mu);
   for (SegLayout& L : g_seg_layouts) (void)hipFree(L.dev);
   g_seg_layouts.clear();
@@ -231,17 +182,17 @@ int tips_adasum_pair(void* dst, const void* a, const void* b, const int64_t* seg
                      void* workspace, int64_t workspace_bytes, void* stream) {
   TRY(check_float(dtype, "tips_adasum_pair"));
   int64_t total;
-  TRY(check_counts(seg_counts, nseg, &total));
+  TRY(check_counts(seg_counts, nseg, "segment", &total));
   if (workspace_bytes < 0) return fail(TIPS_ERR_INVALID_ARG, "negative workspace size");
   if (total == 0) return 0;
   const int64_t need = tips::adasum_workspace_bytes(total, nseg);
   if (workspace_bytes < need)
     return fail(TIPS_ERR_INVALID_ARG, "workspace of %lld B is too small: %lld elements in %d segments need %lld B",
                 (long long)workspace_bytes, (long long)total, nseg, (long long)need);
-  TRY(need_device(dst, "dst"));
-  TRY(need_device(a, "a"));
-  TRY(need_device(b, "b"));
-  TRY(need_device(workspace, "workspace"));
+  TRY(need_device(dst, "dst", kTakes));
+  TRY(need_device(a, "a", kTakes));
+  TRY(need_device(b, "b", kTakes));
+  TRY(need_device(workspace, "workspace", kTakes));
   if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0) return fail(TIPS_ERR_INVALID_ARG, "workspace must be 8-B aligned");
   tips::AdaSegs segs;
   int64_t nchunks;
@@ -253,16 +204,16 @@ int tips_adasum_pair(void* dst, const void* a, const void* b, const int64_t* seg
 int tips_allreduce_adasum(const void* in, void* out, int64_t count, int dtype, void* stream) {
   TRY(check_float(dtype, "tips_allreduce_adasum"));
   if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
-  if (on_negotiation_thread() || negotiation_running()) return fail(TIPS_ERR_UNSUPPORTED, kBusy, "tips_allreduce_adasum");
   State& st = S();
-  std::lock_guard<std::mutex> one(st.adasum_mu);
+  std::unique_lock<std::mutex> one;
+  int size;
+  TRY(side_open(st, st.adasum, "tips_allreduce_adasum", "Adasum", power_of_two, /*rccl_only=*/true, &one, &size));
   int own = 0;
   if (count > 0) {
-    own = need_device(in, "in");
-    if (own == 0) own = need_device(out, "out");
+    own = need_device(in, "in", kTakes);
+    if (own == 0) own = need_device(out, "out", kTakes);
   }
-  int size;
-  TRY(agree(st, "tips_allreduce_adasum", 1, count, dtype, &count, own, &size));
+  TRY(agree(size, 1, count, dtype, &count, own));
   if (count == 0) return 0;
   const int64_t bytes = count * tips::dtype_size(dtype);
   hipStream_t s = (hipStream_t)stream;
@@ -279,18 +230,17 @@ int tips_fused_allreduce_adasum_flat(const void* const* ins, const int64_t* coun
                                      void* stream) {
   TRY(check_float(dtype, "tips_fused_allreduce_adasum_flat"));
   int64_t total;
-  TRY(check_counts(counts, n, &total));
+  TRY(check_counts(counts, n, "segment", &total));
   if (n > 0 && !ins) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list");
-  if (on_negotiation_thread() || negotiation_running())
-    return fail(TIPS_ERR_UNSUPPORTED, kBusy, "tips_fused_allreduce_adasum_flat");
   State& st = S();
-  std::lock_guard<std::mutex> one(st.adasum_mu);
-  int own = 0;
-  if (total > 0) own = need_device(flat, "flat");
-  for (int i = 0; i < n && own == 0; i++)
-    if (counts[i] > 0) own = need_device(ins[i], "a tensor of the list");
+  std::unique_lock<std::mutex> one;
   int size;
-  TRY(agree(st, "tips_fused_allreduce_adasum_flat", n, total, dtype, counts, own, &size));
+  TRY(side_open(st, st.adasum, "tips_fused_allreduce_adasum_flat", "Adasum", power_of_two, /*rccl_only=*/true, &one, &size));
+  int own = 0;
+  if (total > 0) own = need_device(flat, "flat", kTakes);
+  for (int i = 0; i < n && own == 0; i++)
+    if (counts[i] > 0) own = need_device(ins[i], "a tensor of the list", kTakes);
+  TRY(agree(size, n, total, dtype, counts, own));
   if (total == 0) return 0;
   return list_collective(ins, counts, n, dtype, dtype, kOutsFlat, nullptr, flat, /*route=*/false,
                          [&](State& st2, std::vector<BatchItem>& items) -> int {

@@ -268,12 +268,12 @@ int upload(State& st, FusionCache& fc, void* dev, const void* src, size_t bytes)
   return 0;
 }
 
-uint64_t fnv(uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; }
+uint64_t fnv(uint64_t h, uint64_t v) { return (h ^ v) * kFnvPrime; }
 
 Layout* find_layout(State& st, FusionCache& fc, const int64_t* counts, int n, int dtype, const LayoutParams& lp) {
   const int64_t threshold = lp.threshold, tile = lp.tile;
   const bool balance = lp.balance;
-  uint64_t h = fnv(fnv(fnv(fnv(1469598103934665603ull, (uint64_t)dtype), (uint64_t)threshold), (uint64_t)tile),
+  uint64_t h = fnv(fnv(fnv(fnv(kFnvBasis, (uint64_t)dtype), (uint64_t)threshold), (uint64_t)tile),
                    (uint64_t)balance);
   h = fnv(h, (uint64_t)n);
   for (int i = 0; i < n; i++) h = fnv(h, (uint64_t)counts[i]);
@@ -429,7 +429,7 @@ void fill_records(const Layout& L, int mode, const BatchItem* items, const void*
 
 Table* find_table(State& st, FusionCache& fc, Layout& L, int mode, const BatchItem* items, int n,
                   const void* base) {
-  uint64_t h = fnv(fnv(1469598103934665603ull, (uint64_t)mode), (uint64_t)(uintptr_t)base);
+  uint64_t h = fnv(fnv(kFnvBasis, (uint64_t)mode), (uint64_t)(uintptr_t)base);
   for (int i = 0; i < n; i++) h = fnv(fnv(h, (uint64_t)(uintptr_t)items[i].in), (uint64_t)(uintptr_t)items[i].out);
   for (Table* t : L.tables) {
     if (t->hash != h || t->mode != mode || t->base != base) continue;

@@ -7,22 +7,17 @@
 #include <math.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
 
 #include "mxfp8.h"
 #include "rt.h"
+#include "side.h"
 
 using namespace tips::rt;
 
 namespace {
 
-int need_device(const void* p, const char* what) {
-  if (!p) return fail(TIPS_ERR_INVALID_ARG, "null pointer (%s)", what);
-  if (!is_device_ptr(p))
-    return fail(TIPS_ERR_UNSUPPORTED, "%s is host memory: the MXFP8 calls take device pointers only (nothing is staged)", what);
-  return 0;
-}
+const char kTakes[] = "the MXFP8 calls take";  // need_device's phrase
 
 int check_factor(double factor) {
   if (!isfinite(factor) || !isfinite((float)factor)) return fail(TIPS_ERR_INVALID_ARG, "factor %g is not a finite float", factor);
@@ -38,12 +33,8 @@ struct Flat {
 };
 
 int flat_of(const void* const* ptrs, const int64_t* counts, int n, bool cover, Flat* f) {
-  if (n < 0 || (n > 0 && (!counts || !ptrs))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list (n %d)", n);
-  for (int i = 0; i < n; i++) {
-    if (counts[i] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count (tensor %d: %lld)", i, (long long)counts[i]);
-    if (__builtin_add_overflow(f->total, counts[i], &f->total) || f->total > ((int64_t)1 << 56))
-      return fail(TIPS_ERR_INVALID_ARG, "sizes overflow (tensor %d)", i);
-  }
+  if (n > 0 && !ptrs) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list (n %d)", n);
+  TRY(check_counts(counts, n, "tensor", &f->total));
   if (f->total == 0) return 0;
   std::vector<int64_t> offs((size_t)n);
   f->elems = fused_layout(counts, n, TIPS_FLOAT32, offs.data()) / 4;
@@ -64,7 +55,7 @@ int flat_of(const void* const* ptrs, const int64_t* counts, int n, bool cover, F
 }
 
 int check_wire(const void* wire, const char* what) {
-  TRY(need_device(wire, what));
+  TRY(need_device(wire, what, kTakes));
   if ((reinterpret_cast<uintptr_t>(wire) & 15) != 0) return fail(TIPS_ERR_INVALID_ARG, "%s must be 16-B aligned", what);
   return 0;
 }
@@ -82,57 +73,61 @@ int dequantize_from(const Flat& f, const unsigned char* wire, double factor, hip
   return 0;
 }
 
-uint64_t hash_counts(const int64_t* counts, int n) {  // FNV-1a over the counts' bytes
-  uint64_t h = 1469598103934665603ull;
-  for (int i = 0; i < n; i++)
-    for (int k = 0; k < 8; k++) h = (h ^ (((uint64_t)counts[i] >> (8 * k)) & 0xff)) * 1099511628211ull;
-  return h;
-}
-
-const char kBusy[] =
-    "%s does not go through a running negotiation (named MXFP8 requests are not implemented): call it before the "
-    "first named request or after tips_shutdown / tips_init";
-
-// What both collectives check before any device exchange: the lifecycle, the rank count, the
-// algorithm, and that every rank brings the same list and accepts its own pointers
-// (`own`: this rank's verdict, which travels with the record so that no rank waits in the exchange).
-int agree(State& st, const char* what, int n, int64_t total, const int64_t* counts, int own, int* size) {
-  const std::string own_msg = own ? last_error() : std::string();
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-    TRY(set_device(st));
-    *size = st.size;
-    if (st.size > tips::kMxMaxSrcs)
-      return fail(TIPS_ERR_UNSUPPORTED, "%s folds at most %d ranks, not %d", what, tips::kMxMaxSrcs, st.size);
-    if (st.size > 1 && resolve_algo(st.algo, st.size, 0) == TIPS_ALGO_PEER)
-      return fail(TIPS_ERR_UNSUPPORTED, "%s has one schedule, over RCCL send / recv: not available under TIPS_ALGO_PEER", what);
-  }
-  const std::string& msg = own_msg;
-  if (*size > 1) {
-    const int64_t mine[4] = {n, total, (int64_t)hash_counts(counts, n), own};
-    std::vector<int64_t> all((size_t)4 * *size);
-    TRY(tips_allgather_i64(mine, 4, all.data()));
-    for (int r = 0; r < *size; r++) {
-      const int64_t* q = &all[(size_t)4 * r];
-      if (q[0] != all[0] || q[1] != all[1] || q[2] != all[2])
-        return fail(TIPS_ERR_MISMATCH,
-                    "Mismatched MXFP8 allreduce: rank %d has %lld tensors, %lld elements, count hash %llx; rank 0 has %lld "
-                    "tensors, %lld elements, count hash %llx",
-                    r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)all[0], (long long)all[1],
-                    (unsigned long long)all[2]);
-    }
-    for (int r = 0; r < *size; r++)
-      if (all[(size_t)4 * r + 3] != 0 && !own)
-        return fail(TIPS_ERR_MISMATCH, "MXFP8 allreduce: rank %d refused its arguments (status %lld)", r,
-                    (long long)all[(size_t)4 * r + 3]);
-  }
-  if (own) return fail(own, "%s", msg.c_str());
+int at_most_max_srcs(const char* what, int size) {
+  if (size > tips::kMxMaxSrcs)
+    return fail(TIPS_ERR_UNSUPPORTED, "%s folds at most %d ranks, not %d", what, tips::kMxMaxSrcs, size);
   return 0;
 }
 
+// What both collectives check once open, before any device exchange: that every rank brings the
+// same list and accepts its own pointers and stream (`own`: this rank's verdict)
+int agree(int size, int n, int64_t total, const int64_t* counts, int own) {
+  const int64_t mine[4] = {n, total, (int64_t)hash_counts(counts, n), own};
+  SideRecords rec;
+  TRY(side_exchange(size, mine, 4, &rec));
+  // reported in this order: a mismatch, another rank's refusal, this rank's own
+  if (const int r = rec.first_differing(0, 3); r >= 0) {
+    const int64_t *q = rec.of(r), *q0 = rec.of(0);
+    return fail(TIPS_ERR_MISMATCH,
+                "Mismatched MXFP8 allreduce: rank %d has %lld tensors, %lld elements, count hash %llx; rank 0 has %lld "
+                "tensors, %lld elements, count hash %llx",
+                r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)q0[0], (long long)q0[1],
+                (unsigned long long)q0[2]);
+  }
+  if (!own) TRY(rec.report_refusing("MXFP8"));
+  return rec.report_own();
+}
+
+// Blocks of a wire buffer, or of a staged chunk: where their payload and their scales start
+struct Part {
+  unsigned char *payload, *scales;
+  int64_t blocks;
+};
+
+// One RCCL group with every peer q: to(q) goes to q and q's blocks land in from(q), payload then
+// scales each way; a part of no blocks is not exchanged.
+template <class To, class From>
+int exchange(State& st, hipStream_t s, To&& to, From&& from) {
+  TRY(rccl_enter(st, s));
+  NCCL_TRY(ncclGroupStart());
+  for (int q = 0; q < st.size; q++) {
+    if (q == st.rank) continue;
+    const Part t = to(q), f = from(q);
+    if (t.blocks > 0) {
+      NCCL_TRY(ncclSend(t.payload, (size_t)(t.blocks * tips::kMxBlock), ncclInt8, q, st.comm, s));
+      NCCL_TRY(ncclSend(t.scales, (size_t)t.blocks, ncclInt8, q, st.comm, s));
+    }
+    if (f.blocks > 0) {
+      NCCL_TRY(ncclRecv(f.payload, (size_t)(f.blocks * tips::kMxBlock), ncclInt8, q, st.comm, s));
+      NCCL_TRY(ncclRecv(f.scales, (size_t)f.blocks, ncclInt8, q, st.comm, s));
+    }
+  }
+  NCCL_TRY(ncclGroupEnd());
+  return rccl_leave(st, s);
+}
+
 // The schedule: `in` (the segments of this rank's input) -> `out` (the segments of the result), both
-// over the same flat layout. Caller holds st.mu and st.mxfp8_mu.
+// over the same flat layout. Caller holds st.mu and st.mxfp8.mu.
 int run_collective(State& st, const Flat& in, const Flat& out, double factor, hipStream_t s) {
   const int p = st.size, rank = st.rank;
   const int64_t E = in.elems, B = tips::mxfp8_blocks(E), so = tips::mxfp8_scales_offset(E);
@@ -140,64 +135,38 @@ int run_collective(State& st, const Flat& in, const Flat& out, double factor, hi
   // chunk q: blocks chunk_of(B, p, 8, q) - a function of (E, p) alone, payload starts 256-B aligned
   const int64_t per = p > 1 ? chunk_of(B, p, 8, 0).len() : 0;
   const int64_t slot = round_up(per * tips::kMxBlock + per, kAlignBytes);  // a staged chunk: payload, then scales
-  TRY(st.mxfp8_scratch.ensure((size_t)(2 * wire + (p - 1) * slot)));
-  unsigned char* w0 = (unsigned char*)st.mxfp8_scratch.p;
+  TRY(st.mxfp8.open(s, (size_t)(2 * wire + (p - 1) * slot)));
+  unsigned char* w0 = (unsigned char*)st.mxfp8.scratch.p;
   unsigned char* w1 = w0 + wire;
   unsigned char* stage = w1 + wire;
-  if (!st.ev_mxfp8) HIP_TRY(hipEventCreateWithFlags(&st.ev_mxfp8, hipEventDisableTiming));
-  if (st.mxfp8_chain_valid) HIP_TRY(hipStreamWaitEvent(s, st.ev_mxfp8, 0));
   TRY(quantize_into(in, w0, s));
   const unsigned char* reduced = w0;
   if (p > 1) {
     TRY(ensure_comm(st));
     auto slot_of = [&](int r) { return stage + (int64_t)(r < rank ? r : r - 1) * slot; };
+    auto staged = [&](int r, int64_t blocks) { return Part{slot_of(r), slot_of(r) + per * tips::kMxBlock, blocks}; };
+    auto blocks_of = [&](unsigned char* w, Range c) { return Part{w + c.b * tips::kMxBlock, w + so + c.b, c.len()}; };
     const Range mine = chunk_of(B, p, 8, rank);
-    TRY(rccl_enter(st, s));
-    NCCL_TRY(ncclGroupStart());
-    for (int q = 0; q < p; q++) {
-      if (q == rank) continue;
-      const Range c = chunk_of(B, p, 8, q);
-      if (c.len() > 0) {
-        NCCL_TRY(ncclSend(w0 + c.b * tips::kMxBlock, (size_t)(c.len() * tips::kMxBlock), ncclInt8, q, st.comm, s));
-        NCCL_TRY(ncclSend(w0 + so + c.b, (size_t)c.len(), ncclInt8, q, st.comm, s));
-      }
-      if (mine.len() > 0) {
-        NCCL_TRY(ncclRecv(slot_of(q), (size_t)(mine.len() * tips::kMxBlock), ncclInt8, q, st.comm, s));
-        NCCL_TRY(ncclRecv(slot_of(q) + per * tips::kMxBlock, (size_t)mine.len(), ncclInt8, q, st.comm, s));
-      }
-    }
-    NCCL_TRY(ncclGroupEnd());
-    TRY(rccl_leave(st, s));
+    // scatter: chunk q of this rank's buffer to its owner q, the peers' chunks `mine` into their slots
+    TRY(exchange(
+        st, s, [&](int q) { return blocks_of(w0, chunk_of(B, p, 8, q)); }, [&](int q) { return staged(q, mine.len()); }));
     if (mine.len() > 0) {
       tips::MxSrcs srcs = {};
       for (int r = 0; r < p; r++) {
-        srcs.payload[r] = r == rank ? w0 + mine.b * tips::kMxBlock : slot_of(r);
-        srcs.scales[r] = r == rank ? w0 + so + mine.b : slot_of(r) + per * tips::kMxBlock;
+        const Part src = r == rank ? blocks_of(w0, mine) : staged(r, mine.len());
+        srcs.payload[r] = src.payload;
+        srcs.scales[r] = src.scales;
       }
-      HIP_TRY(tips::launch_mxfp8_fold(w1 + mine.b * tips::kMxBlock, w1 + so + mine.b, srcs, p, mine.len(), s));
+      const Part dst = blocks_of(w1, mine);
+      HIP_TRY(tips::launch_mxfp8_fold(dst.payload, dst.scales, srcs, p, mine.len(), s));
     }
-    TRY(rccl_enter(st, s));
-    NCCL_TRY(ncclGroupStart());
-    for (int q = 0; q < p; q++) {
-      if (q == rank) continue;
-      const Range c = chunk_of(B, p, 8, q);
-      if (mine.len() > 0) {
-        NCCL_TRY(ncclSend(w1 + mine.b * tips::kMxBlock, (size_t)(mine.len() * tips::kMxBlock), ncclInt8, q, st.comm, s));
-        NCCL_TRY(ncclSend(w1 + so + mine.b, (size_t)mine.len(), ncclInt8, q, st.comm, s));
-      }
-      if (c.len() > 0) {
-        NCCL_TRY(ncclRecv(w1 + c.b * tips::kMxBlock, (size_t)(c.len() * tips::kMxBlock), ncclInt8, q, st.comm, s));
-        NCCL_TRY(ncclRecv(w1 + so + c.b, (size_t)c.len(), ncclInt8, q, st.comm, s));
-      }
-    }
-    NCCL_TRY(ncclGroupEnd());
-    TRY(rccl_leave(st, s));
+    // gather: the reduced chunk `mine` to every peer, every peer's reduced chunk into its place
+    TRY(exchange(
+        st, s, [&](int) { return blocks_of(w1, mine); }, [&](int q) { return blocks_of(w1, chunk_of(B, p, 8, q)); }));
     reduced = w1;
   }
   TRY(dequantize_from(out, reduced, factor, s));
-  HIP_TRY(hipEventRecord(st.ev_mxfp8, s));
-  st.mxfp8_chain_valid = true;
-  return 0;
+  return st.mxfp8.close(s);
 }
 
 int collective(const char* what, const void* const* ins, const int64_t* counts, int n, void* const* outs, double factor,
@@ -206,20 +175,20 @@ int collective(const char* what, const void* const* ins, const int64_t* counts, 
   Flat in, out;
   TRY(flat_of(ins, counts, n, true, &in));
   TRY(flat_of(outs, counts, n, false, &out));
-  if (on_negotiation_thread() || negotiation_running()) return fail(TIPS_ERR_UNSUPPORTED, kBusy, what);
   State& st = S();
-  std::lock_guard<std::mutex> one(st.mxfp8_mu);
-  // a capturing stream is refused before anything else touches the runtime
+  std::unique_lock<std::mutex> one;
+  int size;
+  TRY(side_open(st, st.mxfp8, what, "MXFP8", at_most_max_srcs, /*rccl_only=*/true, &one, &size));
+  // a capturing stream is this rank's refusal, like a pointer it does not accept
   int own = 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
   else if (cs != hipStreamCaptureStatusNone)
     own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
   for (size_t i = 0; i < in.segs.size() && own == 0; i++)
-    if (in.segs[i].ptr) own = need_device(in.segs[i].ptr, "an input");
-  for (size_t i = 0; i < out.segs.size() && own == 0; i++) own = need_device(out.segs[i].ptr, "an output");
-  int size;
-  TRY(agree(st, what, n, in.total, counts, own, &size));
+    if (in.segs[i].ptr) own = need_device(in.segs[i].ptr, "an input", kTakes);
+  for (size_t i = 0; i < out.segs.size() && own == 0; i++) own = need_device(out.segs[i].ptr, "an output", kTakes);
+  TRY(agree(size, n, in.total, counts, own));
   if (in.total == 0) return 0;
   std::lock_guard<std::mutex> lk(st.mu);
   if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
@@ -228,21 +197,6 @@ int collective(const char* what, const void* const* ins, const int64_t* counts, 
 }
 
 }  // namespace
-
-namespace tips {
-namespace rt {
-
-void mxfp8_release(State& st) {
-  st.mxfp8_scratch.release();
-  if (st.ev_mxfp8) {
-    (void)hipEventDestroy(st.ev_mxfp8);
-    st.ev_mxfp8 = nullptr;
-  }
-  st.mxfp8_chain_valid = false;
-}
-
-}  // namespace rt
-}  // namespace tips
 
 extern "C" {
 
@@ -258,7 +212,7 @@ int tips_mxfp8_quantize(const void* const* ins, const int64_t* counts, int n, vo
   if (f.total == 0) return 0;
   TRY(check_wire(wire, "wire"));
   for (const tips::MxSeg& sg : f.segs)
-    if (sg.ptr) TRY(need_device(sg.ptr, "a tensor of the list"));
+    if (sg.ptr) TRY(need_device(sg.ptr, "a tensor of the list", kTakes));
   return quantize_into(f, (unsigned char*)wire, (hipStream_t)stream);
 }
 
@@ -293,7 +247,7 @@ int tips_mxfp8_dequantize(void* const* outs, const int64_t* counts, int n, const
   TRY(flat_of(outs, counts, n, false, &f));
   if (f.total == 0) return 0;
   TRY(check_wire(wire, "wire"));
-  for (const tips::MxSeg& sg : f.segs) TRY(need_device(sg.ptr, "a tensor of the list"));
+  for (const tips::MxSeg& sg : f.segs) TRY(need_device(sg.ptr, "a tensor of the list", kTakes));
   return dequantize_from(f, (const unsigned char*)wire, factor, (hipStream_t)stream);
 }
 
@@ -308,11 +262,8 @@ int tips_fused_allreduce_mxfp8_flat(const void* const* ins, const int64_t* count
   // the outputs: every tensor at its layout offset in `flat`
   std::vector<int64_t> offs((size_t)n);
   std::vector<void*> outs((size_t)n, nullptr);
-  int64_t total = 0;
-  for (int i = 0; i < n; i++) {
-    if (counts[i] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count (tensor %d: %lld)", i, (long long)counts[i]);
-    total += counts[i] > 0;
-  }
+  int64_t total;
+  TRY(check_counts(counts, n, "tensor", &total));
   if (total > 0) {
     if (!flat) return fail(TIPS_ERR_INVALID_ARG, "null pointer (flat)");
     fused_layout(counts, n, TIPS_FLOAT32, offs.data());

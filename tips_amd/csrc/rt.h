@@ -1,6 +1,7 @@
 // rt.h — internal state and helpers shared by the runtime's translation units
 // (runtime.cc: lifecycle + data-path C-ABI; schedules.cc: ring / direct /
-// simulators; fusion.cc; host_staging.cc; control.cc). Not part of the C-ABI.
+// simulators; fusion.cc; host_staging.cc; control.cc; side.cc: what sparse.cc, adasum.cc and
+// mxfp8.cc share, declared in side.h). Not part of the C-ABI.
 #pragma once
 
 #include <sched.h>
@@ -49,6 +50,8 @@ constexpr int64_t kHostPieceBytes = 16 << 20;
     ncclResult_t r_ = (expr);                                                                          \
     if (r_ != ncclSuccess) return fail(TIPS_ERR_RCCL, "%s failed: %s", #expr, ncclGetErrorString(r_)); \
   } while (0)
+
+constexpr uint64_t kFnvBasis = 1469598103934665603ull, kFnvPrime = 1099511628211ull;  // 64-bit FNV-1a
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline int mod(int a, int p) { return ((a % p) + p) % p; }
@@ -120,6 +123,35 @@ struct EventPool {
       (void)r;
     }
     ev.clear();
+  }
+};
+
+// The scratch of a collective that runs beside the negotiation (side.h). One call at
+// a time uses it (`mu`, taken before State::mu), and a call on another stream first waits for the
+// event the previous call recorded behind its last launch.
+struct SideChain {
+  DevBuf scratch;
+  std::mutex mu;
+  hipEvent_t ev = nullptr;
+  bool valid = false;  // `ev` has been recorded
+  // open and close with State::mu held; a call that fails between the two records nothing
+  int open(hipStream_t s, size_t bytes) {
+    TRY(scratch.ensure(bytes));
+    if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (valid) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
+    return 0;
+  }
+  int close(hipStream_t s) {
+    if (!ev) return 0;  // (released since open: a shutdown between the two)
+    HIP_TRY(hipEventRecord(ev, s));
+    valid = true;
+    return 0;
+  }
+  void release() {
+    scratch.release();
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr;
+    valid = false;
   }
 };
 
@@ -206,25 +238,10 @@ struct State {
   EventPool recv_ev, sum_ev;
   DevBuf staging, host_in, host_out, fusion, small;
   DevBuf cast_scratch;  // fusion.cc, fused casts: a list's tensors of at least the threshold, in the wire type
-  // sparse.cc, tips_sparse_allreduce: the gathered indices, the gathered values and the row-sum's
-  // workspace. One call at a time uses it (sparse_mu), and a call on another stream first waits for
-  // the event the previous call recorded behind its last launch.
-  DevBuf sparse_scratch;
-  std::mutex sparse_mu;
-  hipEvent_t ev_sparse = nullptr;
-  bool sparse_chain_valid = false;
-  // adasum.cc, the Adasum collectives: the partner's buffer, then the pair's workspace (partials and
-  // coefficients). One call at a time (adasum_mu), chained across calling streams like the sparse scratch.
-  DevBuf adasum_scratch;
-  std::mutex adasum_mu;
-  hipEvent_t ev_adasum = nullptr;
-  bool adasum_chain_valid = false;
-  // mxfp8.cc, the MXFP8 collectives: this rank's wire buffer, the reduced wire buffer and the peers'
-  // staged chunks. One call at a time (mxfp8_mu), chained across calling streams like the Adasum scratch.
-  DevBuf mxfp8_scratch;
-  std::mutex mxfp8_mu;
-  hipEvent_t ev_mxfp8 = nullptr;
-  bool mxfp8_chain_valid = false;
+  // the unnegotiated collectives' scratches (side.h), one per feature so that they may run side by side:
+  SideChain sparse;  // sparse.cc: the gathered indices, the gathered values and the row sum's workspace
+  SideChain adasum;  // adasum.cc: the partner's buffer, then the pair's workspace (partials and coefficients)
+  SideChain mxfp8;   // mxfp8.cc: this rank's wire buffer, the reduced wire buffer and the peers' staged chunks
   void* bounce_in = nullptr;  // page-locked kBounceBytes each (hipHostMalloc), for small pageable host tensors
   void* bounce_out = nullptr;
   HostPool* host_pool = nullptr;  // fused host tensors: pack / unpack threads
@@ -371,9 +388,7 @@ int list_collective(const void* const* ins, const int64_t* counts, int n, int dt
 bool on_negotiation_thread();
 // Whether this rank's negotiation runs (synchronous collectives are then routed through it)
 bool negotiation_running();
-void sparse_release(State& st);  // sparse.cc (shutdown)
 void adasum_release(State& st);  // adasum.cc (shutdown: the scratch and the cached segment tables)
-void mxfp8_release(State& st);   // mxfp8.cc (shutdown: the scratch)
 // fusion.cc: the flat call's pack alone - every tensor of the list copied to its fused_layout offset
 // in `flat` (items[i].out = flat), one launch, in the fusion chain. Caller holds st.mu.
 int fused_pack_flat(State& st, const BatchItem* items, int n, int dtype, void* flat, hipStream_t stream);

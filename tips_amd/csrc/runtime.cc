@@ -129,9 +129,9 @@ void tips_shutdown(void) {
   st.fusion.release();
   st.small.release();
   st.cast_scratch.release();
-  sparse_release(st);
+  st.sparse.release();
   adasum_release(st);
-  mxfp8_release(st);
+  st.mxfp8.release();
   st.tuned.clear();
   st.recv_ev.release();
   st.sum_ev.release();

@@ -2,12 +2,11 @@
 // local ordered row sum (sparse_rows.hip), and tips_sparse_allreduce, the collective around it - the
 // other half of the reference's allreduce, its tf.IndexedSlices branch (tips/tensorflow/__init__.py:
 // 59-74), which allgathers values and indices and leaves the sums to the consumer.
-#include <algorithm>
 #include <atomic>
-#include <string>
 #include <vector>
 
 #include "rt.h"
+#include "side.h"
 #include "sparse_rows.h"
 
 using namespace tips::rt;
@@ -34,13 +33,7 @@ int check_rows_args(int64_t rows, int64_t row_elems, int64_t n, int dtype, doubl
   return 0;
 }
 
-int need_device(const void* p, const char* what) {
-  if (!p) return fail(TIPS_ERR_INVALID_ARG, "null pointer (%s)", what);
-  if (!is_device_ptr(p))
-    return fail(TIPS_ERR_UNSUPPORTED, "%s is host memory: the sparse row sum takes device pointers only (nothing is staged)",
-                what);
-  return 0;
-}
+const char kTakes[] = "the sparse row sum takes";  // need_device's phrase
 
 int launch(void* dst, int64_t rows, int64_t row_elems, const void* values, const int64_t* indices, int64_t n, int dtype,
            double pre, double post, void* ws, hipStream_t s) {
@@ -51,21 +44,6 @@ int launch(void* dst, int64_t rows, int64_t row_elems, const void* values, const
 }
 
 }  // namespace
-
-namespace tips {
-namespace rt {
-
-void sparse_release(State& st) {
-  st.sparse_scratch.release();
-  if (st.ev_sparse) {
-    (void)hipEventDestroy(st.ev_sparse);
-    st.ev_sparse = nullptr;
-  }
-  st.sparse_chain_valid = false;
-}
-
-}  // namespace rt
-}  // namespace tips
 
 extern "C" {
 
@@ -85,12 +63,12 @@ int tips_rows_sum(void* dst, int64_t rows, int64_t row_elems, const void* values
   if (workspace_bytes < need)
     return fail(TIPS_ERR_INVALID_ARG, "workspace of %lld B is too small: %lld rows and %lld entries need %lld B",
                 (long long)workspace_bytes, (long long)rows, (long long)n, (long long)need);
-  TRY(need_device(dst, "dst"));
-  TRY(need_device(workspace, "workspace"));
+  TRY(need_device(dst, "dst", kTakes));
+  TRY(need_device(workspace, "workspace", kTakes));
   if ((reinterpret_cast<uintptr_t>(workspace) & 7) != 0) return fail(TIPS_ERR_INVALID_ARG, "workspace must be 8-B aligned");
   if (n > 0) {
-    TRY(need_device(values, "values"));
-    TRY(need_device(indices, "indices"));
+    TRY(need_device(values, "values", kTakes));
+    TRY(need_device(indices, "indices", kTakes));
   }
   return launch(dst, rows, row_elems, values, indices, n, dtype, prescale, postscale, workspace, (hipStream_t)stream);
 }
@@ -99,56 +77,36 @@ int tips_sparse_allreduce(const void* values, const int64_t* indices, int64_t n,
                           int dtype, double prescale, double postscale, void* dense_out, void* stream) {
   bool active;
   TRY(check_rows_args(rows, row_elems, n, dtype, prescale, postscale, &active));
-  if (on_negotiation_thread() || negotiation_running())
-    return fail(TIPS_ERR_UNSUPPORTED,
-                "tips_sparse_allreduce does not go through a running negotiation (named sparse requests are not "
-                "implemented): call it before the first named request or after tips_shutdown / tips_init");
   State& st = S();
-  std::lock_guard<std::mutex> one(st.sparse_mu);
+  std::unique_lock<std::mutex> one;
   int size;
-  {
-    std::lock_guard<std::mutex> lk(st.mu);
-    if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-    TRY(set_device(st));
-    size = st.size;
-  }
+  TRY(side_open(st, st.sparse, "tips_sparse_allreduce", "sparse", nullptr, /*rccl_only=*/false, &one, &size));
   hipStream_t s = (hipStream_t)stream;
-  // this rank's own verdict on its pointers travels with the record, so a rank that refuses its
-  // arguments does not leave the others waiting in the exchange
   int own = 0;
   if (active) {
-    own = need_device(dense_out, "dense_out");
-    if (own == 0 && n > 0) own = need_device(values, "values");
-    if (own == 0 && n > 0) own = need_device(indices, "indices");
+    own = need_device(dense_out, "dense_out", kTakes);
+    if (own == 0 && n > 0) own = need_device(values, "values", kTakes);
+    if (own == 0 && n > 0) own = need_device(indices, "indices", kTakes);
   }
-  const std::string own_msg = own ? last_error() : std::string();
-  std::vector<int64_t> all((size_t)5 * size);
   const int64_t mine[5] = {n, rows, row_elems, dtype, own};
-  if (size == 1) {
-    std::copy(mine, mine + 5, all.begin());
-  } else {
-    TRY(tips_allgather_i64(mine, 5, all.data()));
+  SideRecords rec;
+  TRY(side_exchange(size, mine, 5, &rec));
+  // reported in this order: this rank's own refusal, a mismatch, another rank's refusal
+  TRY(rec.report_own());
+  if (const int r = rec.first_differing(1, 4); r >= 0) {
+    const int64_t *q = rec.of(r), *q0 = rec.of(0);
+    return fail(TIPS_ERR_MISMATCH,
+                "Mismatched sparse allreduce: rank %d has rows %lld, row_elems %lld, dtype %lld; rank 0 has rows %lld, "
+                "row_elems %lld, dtype %lld",
+                r, (long long)q[1], (long long)q[2], (long long)q[3], (long long)q0[1], (long long)q0[2], (long long)q0[3]);
   }
-  if (own) return fail(own, "%s", own_msg.c_str());
-  for (int r = 0; r < size; r++) {
-    const int64_t* q = &all[(size_t)5 * r];
-    if (q[1] != all[1] || q[2] != all[2] || q[3] != all[3])
-      return fail(TIPS_ERR_MISMATCH,
-                  "Mismatched sparse allreduce: rank %d has rows %lld, row_elems %lld, dtype %lld; rank 0 has rows %lld, "
-                  "row_elems %lld, dtype %lld",
-                  r, (long long)q[1], (long long)q[2], (long long)q[3], (long long)all[1], (long long)all[2],
-                  (long long)all[3]);
-  }
-  for (int r = 0; r < size; r++)
-    if (all[(size_t)5 * r + 4] != 0)
-      return fail(TIPS_ERR_MISMATCH, "sparse allreduce: rank %d refused its arguments (status %lld)", r,
-                  (long long)all[(size_t)5 * r + 4]);
+  TRY(rec.report_refusing("sparse"));
   if (!active) return 0;
   const int64_t es = tips::dtype_size(dtype);
   std::vector<int64_t> counts(size), vcounts(size);
   int64_t G = 0;
   for (int r = 0; r < size; r++) {
-    counts[r] = all[(size_t)5 * r];
+    counts[r] = rec.of(r)[0];
     if (counts[r] < 0 || __builtin_add_overflow(G, counts[r], &G))
       return fail(TIPS_ERR_MISMATCH, "sparse allreduce: bad entry count on rank %d", r);
     vcounts[r] = counts[r] * row_elems;
@@ -162,10 +120,8 @@ int tips_sparse_allreduce(const void* values, const int64_t* indices, int64_t n,
   {
     std::lock_guard<std::mutex> lk(st.mu);
     if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-    TRY(st.sparse_scratch.ensure((size_t)(idx_bytes + val_bytes + ws_bytes)));
-    base = (char*)st.sparse_scratch.p;
-    if (!st.ev_sparse) HIP_TRY(hipEventCreateWithFlags(&st.ev_sparse, hipEventDisableTiming));
-    if (st.sparse_chain_valid) HIP_TRY(hipStreamWaitEvent(s, st.ev_sparse, 0));
+    TRY(st.sparse.open(s, (size_t)(idx_bytes + val_bytes + ws_bytes)));
+    base = (char*)st.sparse.scratch.p;
   }
   const int64_t* g_idx = indices;
   const void* g_val = values;
@@ -177,11 +133,7 @@ int tips_sparse_allreduce(const void* values, const int64_t* indices, int64_t n,
   }
   TRY(launch(dense_out, rows, row_elems, g_val, g_idx, G, dtype, prescale, postscale, base + idx_bytes + val_bytes, s));
   std::lock_guard<std::mutex> lk(st.mu);
-  if (st.ev_sparse) {
-    HIP_TRY(hipEventRecord(st.ev_sparse, s));
-    st.sparse_chain_valid = true;
-  }
-  return 0;
+  return st.sparse.close(s);
 }
 
 int tips_sparse_stats(int64_t* calls, int64_t* entries, int64_t* bad_indices) {
