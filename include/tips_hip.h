@@ -376,6 +376,65 @@ TIPS_API int tips_allreduce_mxfp8(const void* in, void* out, int64_t count, doub
 TIPS_API int tips_fused_allreduce_mxfp8_flat(const void* const* ins, const int64_t* counts, int n, void* flat,
                                              double factor, void* stream);
 
+/* ---- MXFP8 error feedback (MXFP8 error feedback) ---- */
+
+/* The MXFP8 wire with a residual carried from one step to the next: each step keeps what its
+ * quantisers dropped and adds it to the next step's input, so that what T steps deliver differs from
+ * the true sum by one bounded residual, not by T roundings. Layout, block, wire buffer, quantise rules
+ * (1)-(4), dequantise and fold are those of the MXFP8 wire above. B = ceil(E / 32) blocks; p ranks;
+ * chunk q = blocks [min(q * per, B), min((q + 1) * per, B)) with per = round_up(ceil(B / p), 8), the
+ * collective's chunk map.
+ *   STATE: one caller-owned device buffer of f32 per list, 16-B aligned, zeroed by the caller before its
+ * first use, of tips_mxfp8_ef_bytes(E, p) = 4 * (round_up(E, 256) + 32 * per) bytes (per = 0 for p = 1).
+ * Elements [0, round_up(E, 256)) are the SENDER RESIDUAL r at the flat layout's positions; the 32 * per
+ * elements behind it are the OWNER RESIDUAL o of this rank's own chunk, element 0 at the chunk's first
+ * element. The state depends on the counts, on p and on the rank: a caller that changes any of them
+ * starts again from zeros.
+ *   Quantise with feedback, per block: c_j = x_j + r_j (one IEEE f32 add, not contracted) at every
+ * position that holds a tensor element; a position that holds none counts as c_j = +0, and its residual
+ * is neither read nor written. If any c_j is NaN or +-Inf the block is poisoned by rule (1) and
+ * r'_j = +0 for its tensor elements - the step is lost, and the residual never carries a non-finite
+ * value into later steps: from a finite state every r' is finite. Otherwise the block of c is quantised
+ * by rules (2)-(3), y_j = decode_e4m3fn(byte_j) * 2^(scale byte - 127) (the dequantise with factor 1)
+ * and r'_j = c_j - y_j (one IEEE f32 subtract) is stored to r. Rule (4) holds: every byte of the wire
+ * buffer is written. With an all-zero residual the wire bytes are those of tips_mxfp8_quantize except
+ * that an input -0 becomes +0 (-0 + +0 = +0) and encodes as 0x00, not 0x80.
+ *   Fold with feedback over sources 0 ... k-1 of a block: acc = ((y0 + y1) + y2) + ... as above, then
+ * c_j = acc_j + o_j (one f32 add after the last source). Poison is judged on c (a poisoned source or an
+ * overflowing sum reaches c as NaN or Inf): a poisoned block sets o'_j = +0; otherwise c is quantised
+ * and o'_j = c_j - y_j stored. The fold knows no tensors: every position of a block is handled alike
+ * (padding positions hold zeros on every source, so their residual stays +0).
+ *   Collective: the schedule of tips_allreduce_mxfp8 with its quantise replaced by the feedback form on
+ * r and the owner's fold by the feedback form on o; dequantise and `factor` unchanged - residuals are
+ * in units of the unscaled sum. p = 1 uses r only: dequantise(quantise_ef(x, r)). A rank whose chunk is
+ * empty launches no fold and leaves o alone. Every rank decodes the same bytes: the outputs are the
+ * same bits on every rank and every run; the states differ per rank by construction. */
+
+/* Bytes of the state of a list of `flat_elems` flat elements on `nranks` (1 ... 16) ranks. Pure host.
+ * < 0 = error. */
+TIPS_API int64_t tips_mxfp8_ef_bytes(int64_t flat_elems, int nranks);
+/* The two local operations with feedback: stream-ordered, no tips_init needed; the checks of
+ * tips_mxfp8_quantize / tips_mxfp8_fold all apply. `residual` is a 16-B aligned device pointer that
+ * overlaps neither the tensors nor a wire buffer (TIPS_ERR_INVALID_ARG; host memory:
+ * TIPS_ERR_UNSUPPORTED): for the quantise the sender residual, round_up(E, 256) floats; for the fold
+ * 32 * block_count floats, element 0 belonging to block `block_begin`. */
+TIPS_API int tips_mxfp8_quantize_ef(const void* const* ins, const int64_t* counts, int n, void* wire, void* residual,
+                                    void* stream);
+TIPS_API int tips_mxfp8_fold_ef(void* dst_wire, const void* const* src_wires, int nsrc, int64_t flat_elems,
+                                int64_t block_begin, int64_t block_count, void* residual, void* stream);
+/* The collectives with feedback over the state `ef` of `ef_bytes` bytes. The checks and refusals of
+ * tips_allreduce_mxfp8 all apply; `ef` is checked like `residual` above, as this rank's own verdict:
+ * it travels in the ranks' host record like a host pointer does, so every rank fails the call together
+ * (TIPS_ERR_MISMATCH "refused its arguments" on the others). An ef_bytes below
+ * tips_mxfp8_ef_bytes(E, size) - a state sized for another list or rank count - is such a verdict and
+ * is TIPS_ERR_MISMATCH on its own rank too. The call kind is part of the compared record: a feedback
+ * call paired with tips_allreduce_mxfp8 / tips_fused_allreduce_mxfp8_flat on another rank returns
+ * TIPS_ERR_MISMATCH on every rank. A call that fails these checks leaves the state untouched. */
+TIPS_API int tips_allreduce_mxfp8_ef(const void* in, void* out, int64_t count, double factor, void* ef, int64_t ef_bytes,
+                                     void* stream);
+TIPS_API int tips_fused_allreduce_mxfp8_ef_flat(const void* const* ins, const int64_t* counts, int n, void* flat,
+                                                double factor, void* ef, int64_t ef_bytes, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

@@ -9,7 +9,7 @@ libtips_hip.so (include/tips_hip.h); there is no CPU fallback.
 import os as _os
 
 from .basics import TipsBasics, init, is_initialized, rank, shutdown, size
-from .compression import Compression, Compressor, FP16Compressor, MXFP8Compressor, NoneCompressor
+from .compression import Compression, Compressor, FP16Compressor, MXFP8Compressor, MXFP8ErrorFeedback, NoneCompressor
 from .ops import (Handle, allgather_async, allgather_op, allreduce_async, broadcast_async, allreduce_async_many, synchronize_many, allreduce_op, broadcast_op, poll, synchronize, broadcast_variables, bucket_sum, fused_allreduce,
                   fused_allreduce_, rank_op, registered_host_buffer, set_algorithm, set_consistency_check, size_op)
 from .ops import fused_allreduce_cast, fused_allreduce_flat, fused_allreduce_host, fused_allreduce_host_flat, fusion_stats
@@ -17,6 +17,7 @@ from .ops import set_op_scaling, allreduce_reduce_op
 from .ops import adasum_op, fused_adasum_flat
 from .ops import (allreduce_mxfp8, fused_allreduce_mxfp8, mxfp8_dequantize, mxfp8_fold, mxfp8_quantize,
                   mxfp8_wire_bytes)
+from .ops import allreduce_mxfp8_ef, fused_allreduce_mxfp8_ef, mxfp8_ef_bytes, mxfp8_fold_ef, mxfp8_quantize_ef
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
@@ -50,6 +51,8 @@ __all__ = [
     "Adasum", "adasum_op", "fused_adasum_flat",
     "MXFP8Compressor", "allreduce_mxfp8", "fused_allreduce_mxfp8", "mxfp8_quantize", "mxfp8_fold", "mxfp8_dequantize",
     "mxfp8_wire_bytes",
+    "MXFP8ErrorFeedback", "allreduce_mxfp8_ef", "fused_allreduce_mxfp8_ef", "mxfp8_ef_bytes", "mxfp8_fold_ef",
+    "mxfp8_quantize_ef",
 ]
 
 
@@ -75,9 +78,13 @@ def _op_scale(op, prescale_factor=1.0, postscale_factor=1.0):
 
 def _no_mxfp8_op(compression, op):
     """Compression.fp8 rides the sum only: Max, Min and Adasum with it raise before any collective."""
-    if compression is MXFP8Compressor and op in (Max, Min, Adasum):
+    if (compression is MXFP8Compressor or _is_ef(compression)) and op in (Max, Min, Adasum):
         raise ValueError("op=%s does not combine with Compression.fp8: the MXFP8 wire carries SUM (and Average) only"
                          % op)
+
+
+def _is_ef(compression):
+    return isinstance(compression, MXFP8ErrorFeedback)
 
 
 def _no_integer_average(tensor, op):
@@ -139,8 +146,19 @@ def allreduce(tensor,
     dequantise. Every other tensor - host, another dtype, sparse, or a call with
     a `name` - travels uncompressed, exactly as under Compression.none. op=Max,
     Min or Adasum with it raises ValueError before any collective.
+
+    compression=Compression.fp8.error_feedback() (an MXFP8ErrorFeedback object,
+    DESIGN.md §17) does the same with the quantisers' residuals carried from call
+    to call (ops.allreduce_mxfp8_ef). The state of a tensor is keyed by
+    (name, numel, device), so `name` is required - without one the call raises
+    ValueError - and it names the state only: the tensor does not become a named
+    request. Tensors that are not dense float32 device tensors travel
+    uncompressed under that name.
     """
     _no_mxfp8_op(compression, op)
+    if _is_ef(compression) and name is None:
+        raise ValueError("allreduce(compression=<MXFP8ErrorFeedback>) needs a name: the tensor's residual state is keyed by "
+                         "(name, numel, device)")
     if op in (Max, Min):
         return _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name)
     if op == Adasum:
@@ -163,6 +181,10 @@ def allreduce(tensor,
     scale = _op_scale(op, prescale_factor, postscale_factor)
     if compression is MXFP8Compressor and name is None and _ops.is_mxfp8_tensor(tensor):
         return allreduce_mxfp8(tensor, 1.0 if scale is None else scale[0] * scale[1])
+    if _is_ef(compression) and _ops.is_mxfp8_tensor(tensor):
+        init()
+        state = compression.tensor_state(name, tensor.numel(), tensor.device, size())
+        return allreduce_mxfp8_ef(tensor, state, 1.0 if scale is None else scale[0] * scale[1])
     tensor_compressed, ctx = compression.compress(tensor)
     if scale is not None:
         summed_tensor_compressed = allreduce_scaled(tensor_compressed, scale[0], scale[1], name=name)
@@ -408,8 +430,18 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
     under set_op_scaling(True); every other gradient (host, another dtype,
     sparse) is reduced uncompressed, exactly as under Compression.none.
     op=Max, Min or Adasum with it raises ValueError.
+
+    Compression.fp8.error_feedback() (an MXFP8ErrorFeedback object, DESIGN.md
+    §17): as Compression.fp8, with the dense float32 device gradients of each
+    device through fused_allreduce_mxfp8_ef over the object's state of
+    (device, counts, size()) - zeros at a signature's first step, carried from
+    step to step after it. fused=False raises ValueError (a state belongs to a
+    list).
     """
     _no_mxfp8_op(compression, op)
+    if _is_ef(compression) and not fused:
+        raise ValueError("allreduce_grads(fused=False) does not combine with MXFP8 error feedback: the residual state "
+                         "belongs to the fused list")
     _no_minmax_grads(op)
     if op == Adasum:
         if gradient_predivide_factor != 1.0:
@@ -469,8 +501,8 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
         outputs views of it (reused as the device flat outputs are);
       - the rest (sparse) one by one, through the reference's allgather branch."""
     _no_minmax_grads(op)
-    if compression is MXFP8Compressor:
-        return _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor)
+    if compression is MXFP8Compressor or _is_ef(compression):
+        return _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor, compression if _is_ef(compression) else None)
     none = compression is Compression.none
     global _DATA_PTR
     if _DATA_PTR is None:
@@ -553,11 +585,14 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
     return out
 
 
-def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor):
+def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor, ef=None):
     """_reduce_grads under Compression.fp8: the dense float32 device gradients through the MXFP8
     collective (per device one fused_allreduce_mxfp8, or one allreduce_mxfp8 each with fused=False),
     the factor prescale * postscale of set_op_scaling multiplied in double; the rest of the list as
-    under Compression.none."""
+    under Compression.none. `ef`: an MXFP8ErrorFeedback - per device one fused_allreduce_mxfp8_ef over
+    its state of (device, counts, size())."""
+    if ef is not None and not fused:
+        raise ValueError("fused=False does not combine with MXFP8 error feedback")
     scale = _average_scale(op, gradient_predivide_factor)
     factor = 1.0 if scale is None else scale[0] * scale[1]
     out, rest, groups = list(grads), [], {}
@@ -571,8 +606,13 @@ def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor):
             rest.append(None)
         else:
             rest.append(g)
-    for members in groups.values():
-        for (i, _), s in zip(members, fused_allreduce_mxfp8([g for _, g in members], factor)):
+    for device, members in groups.items():
+        ts = [g for _, g in members]
+        if ef is None:
+            sums = fused_allreduce_mxfp8(ts, factor)
+        else:
+            sums = fused_allreduce_mxfp8_ef(ts, ef.list_state(device, [g.numel() for g in ts], size()), factor)
+        for (i, _), s in zip(members, sums):
             out[i] = s
     if any(g is not None for g in rest):
         for i, g in enumerate(_reduce_grads(rest, Compression.none, op, fused, gradient_predivide_factor)):

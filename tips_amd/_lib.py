@@ -120,6 +120,17 @@ _SIGNATURES = [
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p]),
     ("tips_fused_allreduce_mxfp8_flat", ctypes.c_int,
      [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p]),
+    ("tips_mxfp8_ef_bytes", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    ("tips_mxfp8_quantize_ef", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("tips_mxfp8_fold_ef", ctypes.c_int,
+     [ctypes.c_void_p, _c_void_pp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("tips_allreduce_mxfp8_ef", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    ("tips_fused_allreduce_mxfp8_ef_flat", ctypes.c_int,
+     [_c_void_pp, _c_i64_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int64,
+      ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

@@ -77,6 +77,80 @@ class MXFP8Compressor(Compressor):
     def decompress(tensor, ctx):
         return tensor
 
+    @staticmethod
+    def error_feedback():
+        """A new stateful compressor for one gradient list: the MXFP8 wire with error feedback."""
+        return MXFP8ErrorFeedback()
+
+
+class MXFP8ErrorFeedback(Compressor):
+    """The MXFP8 wire with error feedback: Compression.fp8.error_feedback(). An object,
+    not a class - it owns the residuals that one gradient list carries from step to step: what the
+    sender's quantiser and the chunk owner's requantiser dropped is added to the next step's input, so
+    that the sum of T steps' outputs differs from the true sum by one bounded residual.
+
+    allreduce_grads / DistributedOptimizer keep one zero-initialised float32 state tensor per
+    (device, counts tuple, size()) - a new signature gets fresh zeros; allreduce(t, name=...) keeps
+    one per (name, numel, device). Everything that is not a dense float32 device tensor travels as
+    under Compression.fp8 (compress / decompress are the identity). reset() drops every state;
+    state_dict() / load_state_dict() carry them through a checkpoint, keyed by signature. The states
+    differ per rank: every rank saves and loads its own."""
+
+    def __init__(self):
+        self._states = {}
+
+    def compress(self, tensor):
+        return tensor, None
+
+    def decompress(self, tensor, ctx):
+        return tensor
+
+    def _state(self, key, device, nbytes):
+        """The state tensor of a signature on `device`: the stored one, or fresh zeros when there is
+        none or its size is not what the call needs (a state of another rank count)."""
+        import torch
+        t = self._states.get(key)
+        if t is None or t.numel() * 4 != nbytes or t.dtype != torch.float32:
+            t = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+        elif t.device != device:  # (loaded from a checkpoint held elsewhere)
+            t = t.to(device)
+        self._states[key] = t
+        return t
+
+    def list_state(self, device, counts, nranks):
+        """The state of a gradient list: float32 [tips_mxfp8_ef_bytes(E, nranks) / 4] on `device`."""
+        from . import ops
+        counts = tuple(int(c) for c in counts)
+        elems, _ = ops.mxfp8_flat_elems(list(counts))
+        return self._state(("list", str(device), counts, int(nranks)), device, ops.mxfp8_ef_bytes(elems, nranks))
+
+    def tensor_state(self, name, numel, device, nranks):
+        """The state of allreduce(t, compression=self, name=name)."""
+        from . import ops
+        elems, _ = ops.mxfp8_flat_elems([int(numel)])
+        return self._state(("tensor", str(name), int(numel), str(device)), device, ops.mxfp8_ef_bytes(elems, nranks))
+
+    def reset(self):
+        """Forget every residual: the next step of every signature starts from zeros."""
+        self._states = {}
+
+    def state_dict(self):
+        """{signature: float32 tensor (a copy)} - what a checkpoint of this rank holds."""
+        return {k: t.detach().clone() for k, t in self._states.items()}
+
+    def load_state_dict(self, state):
+        """Replace every state by copies of `state`'s tensors (a state_dict() of the same rank, rank
+        count and gradient list); a tensor held on another device moves at its first use."""
+        import torch
+        new = {}
+        for k, t in state.items():
+            if not (isinstance(k, tuple) and k and k[0] in ("list", "tensor")):
+                raise ValueError("not a signature of MXFP8ErrorFeedback.state_dict(): %r" % (k,))
+            if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1):
+                raise ValueError("the state of %r is not a flat float32 tensor" % (k,))
+            new[k] = t.detach().clone()
+        self._states = new
+
 
 class Compression(object):
     """Optional gradient compression algorithm used during allreduce (compression.py:69-75)."""

@@ -4,6 +4,9 @@
 // quantises its input once, the blocks are cut into p chunks, chunk q of every rank goes to rank q,
 // which folds the p sources in rank order and requantises once, and the reduced chunks are gathered.
 // A value is quantised twice whatever p is (a ring would requantise at every step).
+// The calls with error feedback (tips_mxfp8_ef_bytes, tips_mxfp8_quantize_ef,
+// tips_mxfp8_fold_ef, tips_allreduce_mxfp8_ef, tips_fused_allreduce_mxfp8_ef_flat) are the same
+// code with a residual: the quantise over the state's sender part, the owner's fold over its owner part.
 #include <math.h>
 
 #include <algorithm>
@@ -60,10 +63,41 @@ int check_wire(const void* wire, const char* what) {
   return 0;
 }
 
-int quantize_into(const Flat& f, unsigned char* wire, hipStream_t s) {
+// `residual`: the sender residual of the feedback form, or null for the plain quantise
+int quantize_into(const Flat& f, unsigned char* wire, float* residual, hipStream_t s) {
   const int64_t so = tips::mxfp8_scales_offset(f.elems);
-  HIP_TRY(tips::launch_mxfp8_quantize(f.segs.data(), (int)f.segs.size(), wire, wire + so, so / tips::kMxBlock,
-                                      tips::mxfp8_wire_bytes(f.elems) - so, s));
+  const int64_t tail_begin = so / tips::kMxBlock, tail_end = tips::mxfp8_wire_bytes(f.elems) - so;
+  if (residual)
+    HIP_TRY(tips::launch_mxfp8_quantize_ef(f.segs.data(), (int)f.segs.size(), wire, wire + so, residual, tail_begin,
+                                           tail_end, s));
+  else
+    HIP_TRY(tips::launch_mxfp8_quantize(f.segs.data(), (int)f.segs.size(), wire, wire + so, tail_begin, tail_end, s));
+  return 0;
+}
+
+// The feedback state of a list of E flat elements on p ranks, in f32 elements: the sender residual
+// (one per flat position up to round_up(E, 256)), then the owner residual of a chunk (32 per block of
+// the largest chunk, chunk 0 - the `per` that sizes a staged slot)
+int64_t ef_sender_elems(int64_t E) { return tips::mxfp8_scales_offset(E); }
+int64_t ef_elems(int64_t E, int p) {
+  const int64_t per = p > 1 ? chunk_of(tips::mxfp8_blocks(E), p, 8, 0).len() : 0;
+  return ef_sender_elems(E) + tips::kMxBlock * per;
+}
+
+// [a, a + an) and [b, b + bn) share a byte
+bool overlaps(const void* a, int64_t an, const void* b, int64_t bn) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return an > 0 && bn > 0 && x < y + (uintptr_t)bn && y < x + (uintptr_t)an;
+}
+
+// a residual / state buffer of `bytes` bytes: a 16-B aligned device pointer that overlaps no tensor of the lists
+int check_residual(const void* r, int64_t bytes, const char* what, const Flat* a, const Flat* b) {
+  TRY(need_device(r, what, kTakes));
+  if ((reinterpret_cast<uintptr_t>(r) & 15) != 0) return fail(TIPS_ERR_INVALID_ARG, "%s must be 16-B aligned", what);
+  for (const Flat* f : {a, b})
+    if (f)
+      for (const tips::MxSeg& sg : f->segs)
+        if (sg.ptr && overlaps(r, bytes, sg.ptr, sg.count * 4)) return fail(TIPS_ERR_INVALID_ARG, "%s overlaps a tensor of the list", what);
   return 0;
 }
 
@@ -81,8 +115,11 @@ int at_most_max_srcs(const char* what, int size) {
 
 // What both collectives check once open, before any device exchange: that every rank brings the
 // same list and accepts its own pointers and stream (`own`: this rank's verdict)
-int agree(int size, int n, int64_t total, const int64_t* counts, int own) {
-  const int64_t mine[4] = {n, total, (int64_t)hash_counts(counts, n), own};
+// (`with_ef`: the call kind is folded into the feedback calls' count-hash word, so that a feedback call
+// paired with a plain call is a mismatch; the plain call's record is what it was)
+int agree(int size, int n, int64_t total, const int64_t* counts, int own, bool with_ef) {
+  const uint64_t h = hash_counts(counts, n);
+  const int64_t mine[4] = {n, total, (int64_t)(with_ef ? (h ^ 0xEFull) * kFnvPrime : h), own};
   SideRecords rec;
   TRY(side_exchange(size, mine, 4, &rec));
   // reported in this order: a mismatch, another rank's refusal, this rank's own
@@ -127,8 +164,9 @@ int exchange(State& st, hipStream_t s, To&& to, From&& from) {
 }
 
 // The schedule: `in` (the segments of this rank's input) -> `out` (the segments of the result), both
-// over the same flat layout. Caller holds st.mu and st.mxfp8.mu.
-int run_collective(State& st, const Flat& in, const Flat& out, double factor, hipStream_t s) {
+// over the same flat layout. `ef`: the feedback state (sender residual, then this rank's owner
+// residual), or null for the plain collective. Caller holds st.mu and st.mxfp8.mu.
+int run_collective(State& st, const Flat& in, const Flat& out, double factor, float* ef, hipStream_t s) {
   const int p = st.size, rank = st.rank;
   const int64_t E = in.elems, B = tips::mxfp8_blocks(E), so = tips::mxfp8_scales_offset(E);
   const int64_t wire = tips::mxfp8_wire_bytes(E);
@@ -139,7 +177,7 @@ int run_collective(State& st, const Flat& in, const Flat& out, double factor, hi
   unsigned char* w0 = (unsigned char*)st.mxfp8.scratch.p;
   unsigned char* w1 = w0 + wire;
   unsigned char* stage = w1 + wire;
-  TRY(quantize_into(in, w0, s));
+  TRY(quantize_into(in, w0, ef, s));
   const unsigned char* reduced = w0;
   if (p > 1) {
     TRY(ensure_comm(st));
@@ -158,7 +196,8 @@ int run_collective(State& st, const Flat& in, const Flat& out, double factor, hi
         srcs.scales[r] = src.scales;
       }
       const Part dst = blocks_of(w1, mine);
-      HIP_TRY(tips::launch_mxfp8_fold(dst.payload, dst.scales, srcs, p, mine.len(), s));
+      if (ef) HIP_TRY(tips::launch_mxfp8_fold_ef(dst.payload, dst.scales, srcs, p, mine.len(), ef + ef_sender_elems(E), s));
+      else HIP_TRY(tips::launch_mxfp8_fold(dst.payload, dst.scales, srcs, p, mine.len(), s));
     }
     // gather: the reduced chunk `mine` to every peer, every peer's reduced chunk into its place
     TRY(exchange(
@@ -169,8 +208,9 @@ int run_collective(State& st, const Flat& in, const Flat& out, double factor, hi
   return st.mxfp8.close(s);
 }
 
+// `with_ef`: the feedback form over the state `ef` of `ef_bytes` bytes
 int collective(const char* what, const void* const* ins, const int64_t* counts, int n, void* const* outs, double factor,
-               hipStream_t s) {
+               bool with_ef, void* ef, int64_t ef_bytes, hipStream_t s) {
   TRY(check_factor(factor));
   Flat in, out;
   TRY(flat_of(ins, counts, n, true, &in));
@@ -188,12 +228,72 @@ int collective(const char* what, const void* const* ins, const int64_t* counts, 
   for (size_t i = 0; i < in.segs.size() && own == 0; i++)
     if (in.segs[i].ptr) own = need_device(in.segs[i].ptr, "an input", kTakes);
   for (size_t i = 0; i < out.segs.size() && own == 0; i++) own = need_device(out.segs[i].ptr, "an output", kTakes);
-  TRY(agree(size, n, in.total, counts, own));
+  if (with_ef && in.total > 0 && own == 0) {
+    const int64_t need = 4 * ef_elems(in.elems, size);
+    if (ef_bytes < need)  // the state was sized for another list or rank count: this rank's verdict
+      own = fail(TIPS_ERR_MISMATCH, "%s: ef_bytes %lld is below tips_mxfp8_ef_bytes(%lld, %d) = %lld", what, (long long)ef_bytes,
+                 (long long)in.elems, size, (long long)need);
+    else own = check_residual(ef, need, "ef", &in, &out);
+  }
+  TRY(agree(size, n, in.total, counts, own, with_ef));
   if (in.total == 0) return 0;
   std::lock_guard<std::mutex> lk(st.mu);
   if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
   TRY(set_device(st));
-  return run_collective(st, in, out, factor, s);
+  return run_collective(st, in, out, factor, with_ef ? (float*)ef : nullptr, s);
+}
+
+// tips_mxfp8_fold and, `with_ef`, tips_mxfp8_fold_ef over `residual` (32 f32 per block of the range)
+int fold_blocks(void* dst_wire, const void* const* src_wires, int nsrc, int64_t flat_elems, int64_t block_begin,
+                int64_t block_count, bool with_ef, void* residual, hipStream_t s) {
+  if (nsrc < 1 || nsrc > tips::kMxMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1 ... %d (got %d)", tips::kMxMaxSrcs, nsrc);
+  if (flat_elems < 0 || flat_elems > ((int64_t)1 << 56) || block_begin < 0 || block_count < 0)
+    return fail(TIPS_ERR_INVALID_ARG, "negative size (elements %lld, blocks %lld + %lld)", (long long)flat_elems,
+                (long long)block_begin, (long long)block_count);
+  if (block_count > tips::mxfp8_blocks(flat_elems) - block_begin)
+    return fail(TIPS_ERR_INVALID_ARG, "blocks %lld + %lld lie outside the buffer's %lld", (long long)block_begin,
+                (long long)block_count, (long long)tips::mxfp8_blocks(flat_elems));
+  if (!src_wires) return fail(TIPS_ERR_INVALID_ARG, "null pointer (src_wires)");
+  if (block_count == 0) return 0;
+  TRY(check_wire(dst_wire, "dst_wire"));
+  const int64_t so = tips::mxfp8_scales_offset(flat_elems);
+  tips::MxSrcs srcs = {};
+  for (int j = 0; j < nsrc; j++) {
+    TRY(check_wire(src_wires[j], "a source wire buffer"));
+    srcs.payload[j] = (const unsigned char*)src_wires[j] + block_begin * tips::kMxBlock;
+    srcs.scales[j] = (const unsigned char*)src_wires[j] + so + block_begin;
+  }
+  unsigned char* d = (unsigned char*)dst_wire;
+  if (!with_ef) {
+    HIP_TRY(tips::launch_mxfp8_fold(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count, s));
+    return 0;
+  }
+  const int64_t rbytes = 4 * tips::kMxBlock * block_count, wbytes = tips::mxfp8_wire_bytes(flat_elems);
+  TRY(check_residual(residual, rbytes, "residual", nullptr, nullptr));
+  bool hit = overlaps(residual, rbytes, dst_wire, wbytes);
+  for (int j = 0; j < nsrc; j++) hit = hit || overlaps(residual, rbytes, src_wires[j], wbytes);
+  if (hit) return fail(TIPS_ERR_INVALID_ARG, "residual overlaps a wire buffer");
+  HIP_TRY(tips::launch_mxfp8_fold_ef(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count,
+                                     (float*)residual, s));
+  return 0;
+}
+
+// the flat list calls: every tensor's result at its layout offset in `flat`
+int flat_collective(const char* what, const void* const* ins, const int64_t* counts, int n, void* flat, double factor,
+                    bool with_ef, void* ef, int64_t ef_bytes, hipStream_t s) {
+  if (n < 0 || (n > 0 && (!counts || !ins))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list (n %d)", n);
+  // the outputs: every tensor at its layout offset in `flat`
+  std::vector<int64_t> offs((size_t)n);
+  std::vector<void*> outs((size_t)n, nullptr);
+  int64_t total;
+  TRY(check_counts(counts, n, "tensor", &total));
+  if (total > 0) {
+    if (!flat) return fail(TIPS_ERR_INVALID_ARG, "null pointer (flat)");
+    fused_layout(counts, n, TIPS_FLOAT32, offs.data());
+    for (int i = 0; i < n; i++)
+      if (counts[i] > 0) outs[i] = (char*)flat + offs[i];
+  }
+  return collective(what, ins, counts, n, outs.data(), factor, with_ef, ef, ef_bytes, s);
 }
 
 }  // namespace
@@ -213,32 +313,36 @@ int tips_mxfp8_quantize(const void* const* ins, const int64_t* counts, int n, vo
   TRY(check_wire(wire, "wire"));
   for (const tips::MxSeg& sg : f.segs)
     if (sg.ptr) TRY(need_device(sg.ptr, "a tensor of the list", kTakes));
-  return quantize_into(f, (unsigned char*)wire, (hipStream_t)stream);
+  return quantize_into(f, (unsigned char*)wire, nullptr, (hipStream_t)stream);
+}
+
+int64_t tips_mxfp8_ef_bytes(int64_t flat_elems, int nranks) {
+  if (flat_elems < 0 || flat_elems > ((int64_t)1 << 56)) return fail(TIPS_ERR_INVALID_ARG, "bad size (%lld elements)", (long long)flat_elems);
+  if (nranks < 1 || nranks > tips::kMxMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nranks must be 1 ... %d (got %d)", tips::kMxMaxSrcs, nranks);
+  return 4 * ef_elems(flat_elems, nranks);
+}
+
+int tips_mxfp8_quantize_ef(const void* const* ins, const int64_t* counts, int n, void* wire, void* residual, void* stream) {
+  Flat f;
+  TRY(flat_of(ins, counts, n, true, &f));
+  if (f.total == 0) return 0;
+  TRY(check_wire(wire, "wire"));
+  for (const tips::MxSeg& sg : f.segs)
+    if (sg.ptr) TRY(need_device(sg.ptr, "a tensor of the list", kTakes));
+  const int64_t rbytes = 4 * ef_sender_elems(f.elems);
+  TRY(check_residual(residual, rbytes, "residual", &f, nullptr));
+  if (overlaps(residual, rbytes, wire, tips::mxfp8_wire_bytes(f.elems))) return fail(TIPS_ERR_INVALID_ARG, "residual overlaps the wire buffer");
+  return quantize_into(f, (unsigned char*)wire, (float*)residual, (hipStream_t)stream);
 }
 
 int tips_mxfp8_fold(void* dst_wire, const void* const* src_wires, int nsrc, int64_t flat_elems, int64_t block_begin,
                     int64_t block_count, void* stream) {
-  if (nsrc < 1 || nsrc > tips::kMxMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1 ... %d (got %d)", tips::kMxMaxSrcs, nsrc);
-  if (flat_elems < 0 || flat_elems > ((int64_t)1 << 56) || block_begin < 0 || block_count < 0)
-    return fail(TIPS_ERR_INVALID_ARG, "negative size (elements %lld, blocks %lld + %lld)", (long long)flat_elems,
-                (long long)block_begin, (long long)block_count);
-  if (block_count > tips::mxfp8_blocks(flat_elems) - block_begin)
-    return fail(TIPS_ERR_INVALID_ARG, "blocks %lld + %lld lie outside the buffer's %lld", (long long)block_begin,
-                (long long)block_count, (long long)tips::mxfp8_blocks(flat_elems));
-  if (!src_wires) return fail(TIPS_ERR_INVALID_ARG, "null pointer (src_wires)");
-  if (block_count == 0) return 0;
-  TRY(check_wire(dst_wire, "dst_wire"));
-  const int64_t so = tips::mxfp8_scales_offset(flat_elems);
-  tips::MxSrcs srcs = {};
-  for (int j = 0; j < nsrc; j++) {
-    TRY(check_wire(src_wires[j], "a source wire buffer"));
-    srcs.payload[j] = (const unsigned char*)src_wires[j] + block_begin * tips::kMxBlock;
-    srcs.scales[j] = (const unsigned char*)src_wires[j] + so + block_begin;
-  }
-  unsigned char* d = (unsigned char*)dst_wire;
-  HIP_TRY(tips::launch_mxfp8_fold(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count,
-                                  (hipStream_t)stream));
-  return 0;
+  return fold_blocks(dst_wire, src_wires, nsrc, flat_elems, block_begin, block_count, false, nullptr, (hipStream_t)stream);
+}
+
+int tips_mxfp8_fold_ef(void* dst_wire, const void* const* src_wires, int nsrc, int64_t flat_elems, int64_t block_begin,
+                       int64_t block_count, void* residual, void* stream) {
+  return fold_blocks(dst_wire, src_wires, nsrc, flat_elems, block_begin, block_count, true, residual, (hipStream_t)stream);
 }
 
 int tips_mxfp8_dequantize(void* const* outs, const int64_t* counts, int n, const void* wire, double factor, void* stream) {
@@ -253,24 +357,23 @@ int tips_mxfp8_dequantize(void* const* outs, const int64_t* counts, int n, const
 
 int tips_allreduce_mxfp8(const void* in, void* out, int64_t count, double factor, void* stream) {
   if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
-  return collective("tips_allreduce_mxfp8", &in, &count, 1, &out, factor, (hipStream_t)stream);
+  return collective("tips_allreduce_mxfp8", &in, &count, 1, &out, factor, false, nullptr, 0, (hipStream_t)stream);
+}
+
+int tips_allreduce_mxfp8_ef(const void* in, void* out, int64_t count, double factor, void* ef, int64_t ef_bytes, void* stream) {
+  if (count < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count");
+  return collective("tips_allreduce_mxfp8_ef", &in, &count, 1, &out, factor, true, ef, ef_bytes, (hipStream_t)stream);
 }
 
 int tips_fused_allreduce_mxfp8_flat(const void* const* ins, const int64_t* counts, int n, void* flat, double factor,
                                     void* stream) {
-  if (n < 0 || (n > 0 && (!counts || !ins))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list (n %d)", n);
-  // the outputs: every tensor at its layout offset in `flat`
-  std::vector<int64_t> offs((size_t)n);
-  std::vector<void*> outs((size_t)n, nullptr);
-  int64_t total;
-  TRY(check_counts(counts, n, "tensor", &total));
-  if (total > 0) {
-    if (!flat) return fail(TIPS_ERR_INVALID_ARG, "null pointer (flat)");
-    fused_layout(counts, n, TIPS_FLOAT32, offs.data());
-    for (int i = 0; i < n; i++)
-      if (counts[i] > 0) outs[i] = (char*)flat + offs[i];
-  }
-  return collective("tips_fused_allreduce_mxfp8_flat", ins, counts, n, outs.data(), factor, (hipStream_t)stream);
+  return flat_collective("tips_fused_allreduce_mxfp8_flat", ins, counts, n, flat, factor, false, nullptr, 0, (hipStream_t)stream);
+}
+
+int tips_fused_allreduce_mxfp8_ef_flat(const void* const* ins, const int64_t* counts, int n, void* flat, double factor,
+                                       void* ef, int64_t ef_bytes, void* stream) {
+  return flat_collective("tips_fused_allreduce_mxfp8_ef_flat", ins, counts, n, flat, factor, true, ef, ef_bytes,
+                         (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// mxfp8.h — the MXFP8 wire format's sizes and the launchers of its three kernels (mxfp8.hip;
-// DESIGN.md §16). Internal to libtips_hip.so (not part of the C-ABI).
+// mxfp8.h — the MXFP8 wire format's sizes and the launchers of its three kernels and of the two
+// with error feedback (mxfp8.hip). Internal to libtips_hip.so (not part of the C-ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,6 +42,15 @@ struct MxSrcs {
 };
 hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
                              int64_t nblocks, hipStream_t s);
+// The two with error feedback. Quantise: `residual` is the sender residual, one f32
+// per flat position from position 0 (16-B aligned, round_up(E, 256) floats); c = x + r is quantised
+// and r' = c - dequantise(c) stored, +0 over a poisoned block; positions without a tensor element are
+// not touched. Fold: `residual` is 32 f32 per block from the range's first block (16-B aligned);
+// c = acc + o is quantised and o' = c - dequantise(c) stored, +0 over a poisoned block.
+hipError_t launch_mxfp8_quantize_ef(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
+                                    float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s);
+hipError_t launch_mxfp8_fold_ef(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
+                                int64_t nblocks, float* residual, hipStream_t s);
 // Dequantise the segments' elements (segs[i].ptr: the f32 destination) from the wire buffer; factor
 // as an f32 multiply behind the decode when it is not 1.
 hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,

@@ -1,4 +1,5 @@
-// mxfp8.hip — the MXFP8 wire: block-scaled 8-bit quantise, fold-requantise and dequantise.
+// mxfp8.hip — the MXFP8 wire: block-scaled 8-bit quantise, fold-requantise and dequantise,
+// and the quantise and the fold with error feedback (defined where their kernels are).
 //
 // The operand is the flat f32 layout of a tensor list (fused_layout: tensors at 256-B aligned offsets).
 // A block is 32 consecutive flat elements; it never straddles two tensors; positions that hold no
@@ -202,6 +203,159 @@ __global__ __launch_bounds__(kBlock) void mxfp8_fold_kernel(unsigned char* dst_p
   if ((g & 1) == 0) dst_scales[blk] = (unsigned char)sb;
 }
 
+// ---- error feedback: the two kernels above with a residual carried between steps ----
+//
+// c = x + r (quantise) or acc + o (fold), one f32 add; c is quantised as above; y = decode(byte) *
+// 2^(scale byte - 127) through decode2 (the fold's conversion and multiply); the new residual c - y,
+// one f32 subtract, replaces the old one - +0 where the block is poisoned, so that a residual never
+// carries a non-finite value. The residual is read once and written once per step and read again
+// only a step later, behind every other byte the step moves: the quantise, whose residual accesses
+// are whole coalesced lines, makes both sides nontemporal; the fold's are measured (below).
+
+// the new residual of 4 elements c whose payload word is w under the scale byte sb (not poisoned)
+__device__ __forceinline__ f32x4 residual4(f32x4 c, unsigned w, unsigned sb) {
+#pragma clang fp contract(off)
+  const float scale = scale_value(sb);
+  const f32x2 lo = decode2<false>(w, scale), hi = decode2<true>(w, scale);
+  return f32x4{c[0] - lo[0], c[1] - lo[1], c[2] - hi[0], c[3] - hi[1]};
+}
+
+// mxfp8_quantize_kernel's launch shape. `residual`: the sender residual, one f32 per flat position
+// (16-B aligned; sg.off is a multiple of 64 and i0 of 4, so a lane's 4 residuals are 16-B aligned
+// whatever the tensor's own address is). Positions that hold no tensor element are neither read nor written.
+__global__ __launch_bounds__(kBlock) void mxfp8_quantize_ef_kernel(MxSegList L, unsigned char* __restrict__ payload,
+                                                                   unsigned char* __restrict__ scales,
+                                                                   float* __restrict__ residual, int64_t tail_begin,
+                                                                   int64_t tail_end) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0)
+    for (int64_t j = tail_begin + tid; j < tail_end; j += kBlock) scales[j] = 0;
+  const int64_t t = blockIdx.x;
+  const int si = seg_of_tile(L, t);
+  const MxSeg sg = L.seg[si];
+  const int64_t base = (t - L.tile0[si]) * kMxTileElems;
+  const float* src = (const float*)sg.ptr;
+  float* res = residual + sg.off;
+  const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+  f32x4 x[kMxRounds], r[kMxRounds];
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {  // all eight loads of the lane before the first use
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    r[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (i0 + 4 <= sg.count) {
+      r[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(res + i0)));
+      if (vec) {
+        x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) x[u][j] = src[i0 + j];
+      }
+    } else if (i0 < sg.count) {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) x[u][j] = src[i0 + j], r[u][j] = res[i0 + j];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    const f32x4 c = x[u] + r[u];  // (positions without a tensor element: +0 + +0)
+    const unsigned am = max8(abs_max4(c));
+    if (i0 >= sg.span) continue;
+    const bool poisoned = am >= kInfBits;
+    const unsigned sb = poisoned ? 255u : scale_byte(am);
+    const unsigned w = poisoned ? 0x7f7f7f7fu : encode4(c, sb);
+    *(unsigned*)(payload + sg.off + i0) = w;
+    if ((tid & 7) == 0) scales[(sg.off + i0) >> 5] = (unsigned char)sb;
+    if (i0 >= sg.count) continue;
+    const f32x4 rn = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c, w, sb);
+    if (i0 + 4 <= sg.count) {
+      st16<true>((u32x4*)(res + i0), __builtin_bit_cast(u32x4, rn));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) res[i0 + j] = rn[j];
+    }
+  }
+}
+
+// mxfp8_fold_kernel's launch shape. `residual`: the owner residual of the range, 32 f32 per block from
+// the range's first block (16-B aligned); every position of a block is read and written. A lane's 16
+// residuals are 64 contiguous bytes, so each of its four 16-B accesses touches a quarter of every
+// 64 B the wave covers and the four together fill the lines: they are plain loads and stores, which
+// lets the caches merge them - measured against the nontemporal forms (profiles/mxfp8_ef/README.md:
+// 34 against 48 us over an eighth of 256 MiB, 16 against 22 us on config 5's list).
+#ifndef TIPS_MXFP8_FOLD_EF_NT_LOAD
+#define TIPS_MXFP8_FOLD_EF_NT_LOAD 0
+#endif
+#ifndef TIPS_MXFP8_FOLD_EF_NT_STORE
+#define TIPS_MXFP8_FOLD_EF_NT_STORE 0
+#endif
+constexpr bool kFoldEfNtLoad = TIPS_MXFP8_FOLD_EF_NT_LOAD, kFoldEfNtStore = TIPS_MXFP8_FOLD_EF_NT_STORE;
+__global__ __launch_bounds__(kBlock) void mxfp8_fold_ef_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
+                                                               MxSrcs srcs, int nsrc, int64_t nblocks,
+                                                               float* __restrict__ residual) {
+#pragma clang fp contract(off)
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t blk = g >> 1;
+  const bool active = blk < nblocks;
+  float acc[16];
+  f32x4 o[4];
+#pragma unroll
+  for (int j = 0; j < 16; j++) acc[j] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; q++) o[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  u32x4* const og = (u32x4*)residual + g * 4;
+  if (active) {
+    u32x4 v = ld16<true>((const u32x4*)srcs.payload[0] + g);
+    unsigned sb = srcs.scales[0][blk];
+#pragma unroll
+    for (int q = 0; q < 4; q++) o[q] = __builtin_bit_cast(f32x4, ld16<kFoldEfNtLoad>(og + q));  // on their way beside source 0
+    for (int k = 0; k < nsrc; k++) {
+      const u32x4 cur = v;
+      const float scale = scale_value(sb);
+      if (k + 1 < nsrc) {
+        v = ld16<true>((const u32x4*)srcs.payload[k + 1] + g);
+        sb = srcs.scales[k + 1][blk];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const f32x2 lo = decode2<false>(cur[q], scale), hi = decode2<true>(cur[q], scale);
+        if (k == 0) {
+          acc[4 * q] = lo[0], acc[4 * q + 1] = lo[1], acc[4 * q + 2] = hi[0], acc[4 * q + 3] = hi[1];
+        } else {
+          acc[4 * q] = acc[4 * q] + lo[0];
+          acc[4 * q + 1] = acc[4 * q + 1] + lo[1];
+          acc[4 * q + 2] = acc[4 * q + 2] + hi[0];
+          acc[4 * q + 3] = acc[4 * q + 3] + hi[1];
+        }
+      }
+    }
+  }
+  f32x4 c[4];
+  unsigned am = 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    c[q] = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]} + o[q];
+    am = max(am, abs_max4(c[q]));
+  }
+  am = max2(am);
+  if (!active) return;
+  const bool poisoned = am >= kInfBits;
+  const unsigned sb = poisoned ? 255u : scale_byte(am);
+  u32x4 w;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    w[q] = poisoned ? 0x7f7f7f7fu : encode4(c[q], sb);
+    const f32x4 on = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c[q], w[q], sb);
+    st16<kFoldEfNtStore>(og + q, __builtin_bit_cast(u32x4, on));
+  }
+  st16<false>((u32x4*)dst_payload + g, w);
+  if ((g & 1) == 0) dst_scales[blk] = (unsigned char)sb;
+}
+
 __device__ __forceinline__ float canonical(float y) {
   return y != y ? __builtin_bit_cast(float, kQuietNaN) : y;
 }
@@ -293,6 +447,29 @@ hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scal
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mxfp8_fold_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
                      nblocks);
+  return hipGetLastError();
+}
+
+hipError_t launch_mxfp8_quantize_ef(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
+                                    float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s) {
+  if (!segs || nseg < 1 || !payload || !scales || !residual) return hipErrorInvalidValue;
+  bool first = true;
+  return for_each_part(segs, nseg, true, [&](const MxSegList& L, unsigned tiles) {
+    hipLaunchKernelGGL(mxfp8_quantize_ef_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales, residual,
+                       first ? tail_begin : (int64_t)0, first ? tail_end : (int64_t)0);
+    first = false;
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_mxfp8_fold_ef(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
+                                int64_t nblocks, float* residual, hipStream_t s) {
+  if (!dst_payload || !dst_scales || nsrc < 1 || nsrc > kMxMaxSrcs || nblocks < 0 || !residual) return hipErrorInvalidValue;
+  if (nblocks == 0) return hipSuccess;
+  const int64_t grid = (2 * nblocks + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mxfp8_fold_ef_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
+                     nblocks, residual);
   return hipGetLastError();
 }
 

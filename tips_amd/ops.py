@@ -734,6 +734,87 @@ def fused_allreduce_mxfp8(tensor_list, factor=1.0):
     return views
 
 
+def mxfp8_ef_bytes(flat_elems, nranks):
+    """Bytes of the error-feedback state of a list of `flat_elems` flat elements on `nranks` ranks
+    (tips_mxfp8_ef_bytes; pure host): 4 * (round_up(E, 256) + 32 * per), the sender
+    residual and the owner residual of the largest chunk (per = 0 on one rank)."""
+    return int(_lib.call("tips_mxfp8_ef_bytes", int(flat_elems), int(nranks)))
+
+
+def _check_mxfp8_state(t, what):
+    if not (is_mxfp8_tensor(t) and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous float32 device tensor" % what)
+
+
+def mxfp8_quantize_ef(tensor_list, residual, wire=None):
+    """mxfp8_quantize with error feedback (tips_mxfp8_quantize_ef): c = x + residual is quantised and
+    residual = c - dequantise(c) is left for the next step, +0 over a poisoned block. `residual`: a
+    float32 device tensor of round_up(E, 256) elements at the flat layout's positions, 16-B aligned,
+    zeros before the first step; updated in place."""
+    import torch
+    _check_mxfp8_list(tensor_list, "mxfp8_quantize_ef")
+    _check_mxfp8_state(residual, "residual")
+    counts = [t.numel() for t in tensor_list]
+    elems, _ = mxfp8_flat_elems(counts)
+    nbytes, so = mxfp8_wire_bytes(elems)
+    if residual.numel() < so:
+        raise ValueError("residual holds %d elements, the list's flat layout needs %d" % (residual.numel(), so))
+    if wire is None:
+        wire = torch.empty(nbytes, dtype=torch.uint8, device=tensor_list[0].device if tensor_list else "cuda")
+    if tensor_list:
+        pp, _k1 = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+        cp, _k2 = _lib.i64_array(counts)
+        _lib.call("tips_mxfp8_quantize_ef", pp, cp, len(counts), wire.data_ptr(), residual.data_ptr(),
+                  tensors.stream_of(tensor_list[0]))
+    return wire
+
+
+def mxfp8_fold_ef(dst_wire, src_wires, flat_elems, block_begin, block_count, residual):
+    """mxfp8_fold with error feedback (tips_mxfp8_fold_ef): c = acc + residual is quantised and
+    residual = c - dequantise(c) kept. `residual`: 32 * block_count float32 device elements, element 0
+    belonging to block `block_begin`; updated in place."""
+    _check_mxfp8_state(residual, "residual")
+    if residual.numel() < 32 * int(block_count):
+        raise ValueError("residual holds %d elements, %d blocks need %d" % (residual.numel(), block_count, 32 * block_count))
+    pp, _k1 = _lib.ptr_array([w.data_ptr() for w in src_wires])
+    _lib.call("tips_mxfp8_fold_ef", dst_wire.data_ptr(), pp, len(src_wires), int(flat_elems), int(block_begin),
+              int(block_count), residual.data_ptr(), tensors.stream_of(dst_wire))
+    return dst_wire
+
+
+def allreduce_mxfp8_ef(tensor, state, factor=1.0):
+    """allreduce_mxfp8 with error feedback (tips_allreduce_mxfp8_ef): `state` is the
+    caller's float32 device tensor of mxfp8_ef_bytes(E, size()) bytes, zeros before the first step,
+    updated in place - the sender residual and this rank's owner residual."""
+    if not is_mxfp8_tensor(tensor):
+        raise ValueError("allreduce_mxfp8_ef takes a dense float32 device tensor")
+    _check_mxfp8_state(state, "state")
+    basics.init()
+    src = tensors.contiguous(tensor)
+    out = tensors.empty_like(src)
+    n = tensors.numel(src)
+    if n:
+        _lib.call("tips_allreduce_mxfp8_ef", tensors.data_ptr(src), tensors.data_ptr(out), n, float(factor),
+                  state.data_ptr(), state.numel() * 4, tensors.stream_of(src))
+    return out
+
+
+def fused_allreduce_mxfp8_ef(tensor_list, state, factor=1.0):
+    """fused_allreduce_mxfp8 with error feedback (tips_fused_allreduce_mxfp8_ef_flat): one state
+    tensor for the list, as allreduce_mxfp8_ef's."""
+    if not tensor_list:
+        return []
+    _check_mxfp8_list(tensor_list, "fused_allreduce_mxfp8_ef")
+    _check_mxfp8_state(state, "state")
+    basics.init()
+    fo = _flat_outputs(tensor_list, _lib.FLOAT32)
+    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+    flat, views = fo.take()
+    _lib.call("tips_fused_allreduce_mxfp8_ef_flat", pp[0], fo.cp[0], len(tensor_list), flat.data_ptr(), float(factor),
+              state.data_ptr(), state.numel() * 4, _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+    return views
+
+
 def _flat_call(tensor_list, code, ptrs, scale=None):
     return _flat_run(_flat_outputs(tensor_list, code), tensor_list, ptrs, scale)
 

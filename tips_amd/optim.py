@@ -639,7 +639,9 @@ def DistributedOptimizer(optimizer,
     """Same arguments and validation as the reference (__init__.py:337-456); `optimizer` is a
     torch.optim.Optimizer. name / use_locking / device_* are accepted for signature compatibility.
     Under set_op_scaling(True), op=Average (the default) divides by size() inside the reduction and
-    gradient_predivide_factor f moves 1/f of it before the sums (for 16-bit gradients)."""
+    gradient_predivide_factor f moves 1/f of it before the sums (for 16-bit gradients).
+    compression=Compression.fp8.error_feedback() keeps its residual state in that object from step
+    to step: pass one object per optimizer and checkpoint its state_dict() per rank."""
     if op == 'Adasum':
         raise ValueError('op=Adasum is not supported by DistributedOptimizer: Horovod applies Adasum there to weight '
                          'deltas, not gradients, and that wrapper is not implemented. Reduce gradients with '
