@@ -26,6 +26,20 @@ extern "C" {
 TIPS_API int64_t tips_fusion_tile_table(const int64_t* counts, int n, int dtype, const int64_t* ins, const int64_t* outs,
                                        int64_t* records, int64_t cap, int64_t* ntiles, int64_t* tile_bytes);
 
+/* The same for any of the four table kinds fusion.cc uploads (mode: 0 = the bucket slots' pack and
+ * unpack tables of the fused allreduce, 1 = the out-of-place copy above, 2 = the flat output's pack,
+ * 3 = the fused cast's pack and unpack tables: float32 tensors, `dtype` the 16-bit wire type whose
+ * bytes the layout counts, the float32 side of virtual byte v at its record's base + 2 v). `base` is
+ * the slot base (modes 0 and 3: bucket b at base + (b % 2) * threshold) or the flat output (mode 2).
+ * Modes 0 and 3 return two tables back to back, pack then unpack, each [2 per tile | 1 per segment];
+ * the layout is the mode's own (the cast's tile for mode 3). buckets (may be NULL; room for
+ * bucket_cap): 4 x int64 per bucket {byte offset, bytes, first tile, tiles}; *nbuckets their number.
+ * Returns the record count over all tables (records may be NULL to ask) or < 0. */
+TIPS_API int64_t tips_fusion_mode_table(const int64_t* counts, int n, int dtype, int mode, const int64_t* ins,
+                                       const int64_t* outs, int64_t base, int64_t* records, int64_t cap,
+                                       int64_t* ntiles, int64_t* tile_bytes, int64_t* buckets, int64_t bucket_cap,
+                                       int64_t* nbuckets);
+
 /* Host-copy pool check (no GPU): `runs` back-to-back fork-join runs of njobs (every third run
  * njobs / 2) on a pool of nthreads; TIPS_OK when every job of every run ran exactly once. For the
  * CPU tests of the pool behind tips_fused_allreduce_host. */

@@ -65,7 +65,7 @@ def test_product_and_development_exports():
     assert prod == set(header_functions())
     assert not prod & dev_only
     assert dev == prod | dev_only
-    assert len(dev_only) == 15  # simulators (4), self-tests (3), sweeps (4), tips_schedule_plan, tile table,
+    assert len(dev_only) == 16  # simulators (4), self-tests (3), sweeps (4), tips_schedule_plan, tile tables (2),
     #                             tips_tune_candidates, tips_multi_sum_remote
     from tips_amd import _lib
     D, L = _lib.dev(), _lib.lib()

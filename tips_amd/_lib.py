@@ -206,6 +206,9 @@ _SIGNATURES = [
 _DEV_SIGNATURES = [
     ("tips_fusion_tile_table", ctypes.c_int64,
      [_c_i64_p, ctypes.c_int, ctypes.c_int, _c_i64_p, _c_i64_p, _c_i64_p, ctypes.c_int64, _c_i64_p, _c_i64_p]),
+    ("tips_fusion_mode_table", ctypes.c_int64,
+     [_c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i64_p, _c_i64_p, ctypes.c_int64, _c_i64_p, ctypes.c_int64,
+      _c_i64_p, _c_i64_p, _c_i64_p, ctypes.c_int64, _c_i64_p]),
     ("tips_host_pool_selftest", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     ("tips_negotiation_selftest", ctypes.c_int,
      [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int64]),

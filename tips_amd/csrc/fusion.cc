@@ -1062,6 +1062,48 @@ int64_t tips_fusion_tile_table(const int64_t* counts, int n, int dtype, const in
   }
   return (int64_t)rec.size();
 }
+
+int64_t tips_fusion_mode_table(const int64_t* counts, int n, int dtype, int mode, const int64_t* ins,
+                               const int64_t* outs, int64_t base, int64_t* records, int64_t cap, int64_t* ntiles,
+                               int64_t* tile_bytes, int64_t* buckets, int64_t bucket_cap, int64_t* nbuckets) {
+  TRY(check_dtype(dtype));
+  if (mode != kSlot && mode != kCopy && mode != kFlat && mode != kSlotCast)
+    return fail(TIPS_ERR_INVALID_ARG, "tips_fusion_mode_table: mode %d", mode);
+  if (mode == kSlotCast && dtype != TIPS_FLOAT16 && dtype != TIPS_BFLOAT16)
+    return fail(TIPS_ERR_UNSUPPORTED, "tips_fusion_mode_table: the cast tables are laid out in a 16-bit wire type");
+  if (n < 0 || (n > 0 && (!counts || !ins || !outs))) return fail(TIPS_ERR_INVALID_ARG, "bad list");
+  for (int i = 0; i < n; i++)
+    if (counts[i] < 0) return fail(TIPS_ERR_INVALID_ARG, "negative count %d", i);
+  Layout L;
+  build_layout(&L, dtype, layout_params(/*cast=*/mode == kSlotCast), counts, n);
+  std::vector<BatchItem> items((size_t)n);
+  for (int i = 0; i < n; i++) {
+    // (as tips_fused_allreduce_flat's entry: every flat item's output is the flat buffer)
+    const int64_t out = mode == kFlat ? (counts[i] ? base : 0) : outs[i];
+    items[i] = BatchItem{(const void*)(uintptr_t)ins[i], (void*)(uintptr_t)out, counts[i]};
+  }
+  std::vector<tips::CopySeg> rec;
+  fill_records(L, mode, items.data(), mode == kCopy ? nullptr : (const void*)(uintptr_t)base, &rec);
+  if (ntiles) *ntiles = L.ntiles;
+  if (tile_bytes) *tile_bytes = L.tile;
+  if (nbuckets) *nbuckets = (int64_t)L.buckets.size();
+  if (buckets) {
+    if (bucket_cap < (int64_t)L.buckets.size())
+      return fail(TIPS_ERR_INVALID_ARG, "tips_fusion_mode_table: %zu buckets, room for %lld", L.buckets.size(),
+                  (long long)bucket_cap);
+    for (size_t b = 0; b < L.buckets.size(); b++) {
+      const Bucket& bk = L.buckets[b];
+      const int64_t v[4] = {bk.off, bk.bytes, bk.tile0, bk.ntiles};
+      memcpy(buckets + 4 * b, v, sizeof v);
+    }
+  }
+  if (records) {
+    if (cap < (int64_t)rec.size())
+      return fail(TIPS_ERR_INVALID_ARG, "tips_fusion_mode_table: %zu records, room for %lld", rec.size(), (long long)cap);
+    memcpy(records, rec.data(), rec.size() * sizeof(tips::CopySeg));
+  }
+  return (int64_t)rec.size();
+}
 #endif  // TIPS_DEV
 
 int64_t tips_fused_layout(const int64_t* counts, int n, int dtype, int64_t* offsets) {
