@@ -8,12 +8,13 @@ SRCS     := tips_amd/csrc/kernels.hip tips_amd/csrc/runtime.cc tips_amd/csrc/rt_
             tips_amd/csrc/fusion.cc tips_amd/csrc/host_staging.cc tips_amd/csrc/control.cc tips_amd/csrc/negotiate.cc tips_amd/csrc/peer.cc \
             tips_amd/csrc/bootstrap.cc tips_amd/csrc/neg_protocol.cc tips_amd/csrc/err.cc \
             tips_amd/csrc/sparse_rows.hip tips_amd/csrc/sparse.cc tips_amd/csrc/adasum.hip tips_amd/csrc/adasum.cc \
-            tips_amd/csrc/mxfp8.hip tips_amd/csrc/mxfp8.cc tips_amd/csrc/side.cc
+            tips_amd/csrc/mxfp8.hip tips_amd/csrc/mxfp8.cc tips_amd/csrc/side.cc \
+            tips_amd/csrc/reducescatter.hip tips_amd/csrc/reducescatter.cc
 # the tuning sweeps' kernels: the development and sanitizer libraries only
 DEV_SRCS := tips_amd/csrc/kernels_dev.hip
 HDRS     := tips_amd/csrc/kernels.h tips_amd/csrc/kernels_device.h tips_amd/csrc/kernels_dev.h tips_amd/csrc/rt.h tips_amd/csrc/net.h tips_amd/csrc/plan.h include/tips_hip.h \
             include/tips_hip_dev.h tips_amd/csrc/err.h tips_amd/csrc/neg_protocol.h tips_amd/csrc/sparse_rows.h tips_amd/csrc/adasum.h \
-            tips_amd/csrc/mxfp8.h tips_amd/csrc/side.h
+            tips_amd/csrc/mxfp8.h tips_amd/csrc/side.h tips_amd/csrc/reducescatter.h
 DEVLIB   := tools/lib/libtips_hip_dev.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fno-gpu-flush-denormals-to-zero -Wall -Wno-unused-result -fvisibility=hidden
 

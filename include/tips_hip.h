@@ -435,6 +435,67 @@ TIPS_API int tips_allreduce_mxfp8_ef(const void* in, void* out, int64_t count, d
 TIPS_API int tips_fused_allreduce_mxfp8_ef_flat(const void* const* ins, const int64_t* counts, int n, void* flat,
                                                 double factor, void* ef, int64_t ef_bytes, void* stream);
 
+/* ---- reduce-scatter (Reduce-scatter) ---- */
+
+/* One definition for the calls below. ROW SPLIT: a contiguous tensor of shape [rows, ...] with
+ * row_elems = the product of its trailing dimensions (1 for a 1-D tensor) is split along dimension 0
+ * as Horovod's reducescatter does: with base = rows / p and rem = rows % p, rank q owns
+ * base + (q < rem) rows from row q * base + min(q, rem); a rank may own none. RESULT: rank q's output
+ * for tensor i has its own rows; element k is, for TIPS_OP_SUM, post * (((pre * x_0[k]) + (pre * x_1[k]))
+ * + ... + (pre * x_{p-1}[k])) with x_r rank r's slice q, ranks ascending, in the working type (fp32
+ * for FLOAT32 / FLOAT16 / BFLOAT16, f64 for FLOAT64, the storage type for the integers), every multiply
+ * and add a separate IEEE operation and one rounding at the store - tips_multi_sum_scaled's fold, with
+ * both factors 1 tips_multi_sum's; for TIPS_OP_MAX / TIPS_OP_MIN the exact compare of
+ * tips_multi_reduce, without factors. The same bits on every run, and bit for bit the slice of what the
+ * direct allreduce computes from the same inputs. REGION q of a list of n tensors is the
+ * concatenation of every tensor's slice q in list order, each non-empty slice at the next multiple of
+ * 256 bytes, empty slices taking no space: a function of (rows[], row_elems[], dtype, p, q) alone.
+ *   Checks of the three device calls: an unknown dtype or op, a factor that is not finite and MAX / MIN
+ * with a factor other than 1 return TIPS_ERR_INVALID_ARG, an integer dtype with a factor other than 1
+ * TIPS_ERR_UNSUPPORTED; negative sizes and null lists TIPS_ERR_INVALID_ARG. Every pointer is a device
+ * pointer aligned to its element: the collectives answer a host pointer with TIPS_ERR_UNSUPPORTED
+ * (nothing is staged); tips_reducescatter_fold, like tips_multi_sum, does not probe its pointers. */
+
+/* Pure host: the rows rank `rank` of `nranks` owns of a [rows, ...] tensor; *begin (may be NULL) = its
+ * first row. < 0 = error. */
+TIPS_API int64_t tips_reducescatter_rows(int64_t rows, int nranks, int rank, int64_t* begin);
+/* Pure host: the bytes of region `rank` (up to its last slice's last byte); offsets[i] (offsets may be
+ * NULL) = the byte offset of tensor i's slice in it. < 0 = error. */
+TIPS_API int64_t tips_reducescatter_layout(const int64_t* rows, const int64_t* row_elems, int n, int dtype, int nranks,
+                                           int rank, int64_t* offsets);
+/* The kernel alone: stream-ordered, no communication, no tips_init needed. outs[i][k] for k < counts[i]
+ * = the fold over sources j < nsrc in ascending j, where source own_pos is own[i] and source
+ * j != own_pos is (char*)stages[j] + offsets[i] (stages[own_pos] is ignored and may be NULL; stages
+ * may be NULL when nsrc is 1, which is the - scaled - copy). nsrc outside 1 ... 16, own_pos outside
+ * 0 ... nsrc - 1, an offset that is no multiple of 256, segments that do not ascend without overlap,
+ * a stage that is not 16-B aligned and a null pointer of a non-empty segment return
+ * TIPS_ERR_INVALID_ARG. A segment of 0 elements is legal and touches nothing. Outputs must overlap
+ * neither the own slices nor the stages. */
+TIPS_API int tips_reducescatter_fold(void* const* outs, const void* const* own, const int64_t* counts,
+                                     const int64_t* offsets, int n, const void* const* stages, int nsrc, int own_pos,
+                                     int dtype, int op, double prescale, double postscale, void* stream);
+/* The collective over one tensor, out of place, ordered on the caller's stream: `in` holds
+ * rows * row_elems elements, `out` this rank's rows of them. Slice q goes to rank q straight from `in`
+ * and every peer's slice `rank` arrives in runtime scratch, all in one RCCL group; one launch folds
+ * the p sources in rank order into `out`. The ranks first compare {tensors, elements, a hash of the
+ * (rows, row_elems) list, dtype, op, the factors' bits} on the host (the gather behind
+ * tips_allgather_i64): a difference returns TIPS_ERR_MISMATCH ("Mismatched reduce-scatter ...") on every
+ * rank before any device exchange. This rank's verdict on its own arguments - the checks above, an
+ * output that overlaps an input (TIPS_ERR_INVALID_ARG), a stream that is being captured
+ * (TIPS_ERR_UNSUPPORTED) - travels in that record, so the other ranks return TIPS_ERR_MISMATCH "refused
+ * its arguments" and nobody waits. More than 16 ranks, TIPS_ALGO_PEER and a running negotiation (named
+ * reduce-scatter requests are not implemented) return TIPS_ERR_UNSUPPORTED; every other algorithm
+ * setting is ignored. A total of 0 elements is TIPS_OK; a rank that owns no row takes part in the
+ * exchange and launches nothing. One rank: the (scaled) copy. */
+TIPS_API int tips_reducescatter(const void* in, void* out, int64_t rows, int64_t row_elems, int dtype, int op,
+                                double prescale, double postscale, void* stream);
+/* The collective over a list of n tensors of one dtype: region q, packed into runtime scratch (one
+ * launch per 112 peer slices), goes to rank q in one RCCL group; the fold writes every outs[i] from the staged regions and
+ * this rank's own slices of ins[i]. The same checks and refusals as tips_reducescatter. */
+TIPS_API int tips_grouped_reducescatter(const void* const* ins, void* const* outs, const int64_t* rows,
+                                        const int64_t* row_elems, int n, int dtype, int op, double prescale,
+                                        double postscale, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

@@ -53,7 +53,36 @@ __all__ = [
     "mxfp8_wire_bytes",
     "MXFP8ErrorFeedback", "allreduce_mxfp8_ef", "fused_allreduce_mxfp8_ef", "mxfp8_ef_bytes", "mxfp8_fold_ef",
     "mxfp8_quantize_ef",
+    "reducescatter", "grouped_reducescatter",
 ]
+
+
+def reducescatter(tensor, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None):
+    """This rank's rows of the reduction of `tensor` over all ranks (Horovod's reducescatter;
+    tips_reducescatter; DESIGN.md, Reduce-scatter).
+
+    `tensor` [rows, ...] is split along dimension 0: with base = rows // size() and rem = rows % size(),
+    rank q owns base + (q < rem) rows from row q * base + min(q, rem), possibly none. Returns a new
+    tensor [own rows, ...] of the same dtype holding postscale_factor * SUM over ranks of
+    (prescale_factor * x), ranks in ascending order, in fp32 (f64 for float64, the integer type for
+    integers), every multiply and add a separate operation and one rounding at the store: the same
+    bits on every run, and bit for bit that slice of the direct allreduce, so
+    allgather_op(reducescatter(x, op=Sum)) is allreduce's result under TIPS_ALGO=direct. op=Average
+    divides by size() through the postscale factor, whatever set_op_scaling says; op=Max / Min are the
+    exact compares of allreduce_reduce_op. A dense device torch tensor (made contiguous if it is not)
+    of float32, float64, float16, bfloat16, int32 or int64; the same op, factors and shape on every
+    rank. ValueError, before anything is initialised, for a 0-dim, host or sparse tensor, an integer
+    dtype with op=Average or a factor, op=Max / Min with a factor, op=Adasum, and a `name` (named
+    requests carry SUM allreduce only)."""
+    return _ops.grouped_reducescatter_op([tensor], op, prescale_factor, postscale_factor, name)[0]
+
+
+def grouped_reducescatter(tensors, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None):
+    """reducescatter of every tensor of a list, one exchange and one fold launch per (dtype, device)
+    group (tips_grouped_reducescatter): rank q receives every tensor's slice q in one RCCL group and
+    the fold writes the outputs straight from the staged bytes. Returns the list of this rank's
+    shards; None entries pass through. Arguments and refusals as reducescatter."""
+    return _ops.grouped_reducescatter_op(tensors, op, prescale_factor, postscale_factor, name)
 
 
 def allreduce_scaled(tensor, prescale_factor=1.0, postscale_factor=1.0, name=None):

@@ -1,0 +1,315 @@
+// reducescatter.cc — the reduce-scatter entry points of the C-ABI: the two pure-host
+// layout calls, tips_reducescatter_fold (reducescatter.hip's kernel alone) and the collectives
+// tips_reducescatter / tips_grouped_reducescatter around it: every rank sends slice q of its tensors to
+// rank q in one RCCL group and folds the p sources of its own slices in rank order, straight into the
+// callers' outputs. It is the direct schedule's first half: the same fold over the same operands, so a
+// shard is bit-identical to that slice of the direct allreduce.
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "reducescatter.h"
+#include "rt.h"
+#include "side.h"
+
+using namespace tips::rt;
+
+namespace {
+
+const char kTakes[] = "the reduce-scatter takes";  // need_device's phrase
+
+int at_most_max_srcs(const char* what, int size) {
+  if (size > tips::kMaxSrcs) return fail(TIPS_ERR_UNSUPPORTED, "%s folds at most %d ranks, not %d", what, tips::kMaxSrcs, size);
+  return 0;
+}
+
+// dtype, op and factors: what every entry checks the same way
+int check_op(int dtype, int op, double pre, double post) {
+  TRY(check_dtype(dtype));
+  if (op != TIPS_OP_SUM && op != TIPS_OP_MAX && op != TIPS_OP_MIN) return fail(TIPS_ERR_INVALID_ARG, "unknown op %d", op);
+  TRY(check_scale(dtype, pre, post));
+  if (op != TIPS_OP_SUM && (pre != 1.0 || post != 1.0))
+    return fail(TIPS_ERR_INVALID_ARG, "there is no scaled MAX / MIN (prescale %g, postscale %g)", pre, post);
+  return 0;
+}
+
+tips::Scale scale_of(int op, double pre, double post) {
+  tips::Scale sc;
+  sc.pre = pre;
+  sc.post = post;
+  sc.op = op;
+  return sc;
+}
+
+// rows and row_elems of a list: none negative, no tensor's or region's bytes overflow; *total = elements
+int check_shapes(const int64_t* rows, const int64_t* row_elems, int n, int es, int64_t* total) {
+  if (n < 0 || (n > 0 && (!rows || !row_elems))) return fail(TIPS_ERR_INVALID_ARG, "bad tensor list (n %d)", n);
+  *total = 0;
+  for (int i = 0; i < n; i++) {
+    int64_t elems;
+    if (rows[i] < 0 || row_elems[i] < 0)
+      return fail(TIPS_ERR_INVALID_ARG, "negative size (tensor %d: rows %lld, row_elems %lld)", i, (long long)rows[i],
+                  (long long)row_elems[i]);
+    if (__builtin_mul_overflow(rows[i], row_elems[i], &elems) || __builtin_add_overflow(*total, elems, total) ||
+        *total > ((int64_t)1 << 56) / es)
+      return fail(TIPS_ERR_INVALID_ARG, "sizes overflow (tensor %d)", i);
+  }
+  return 0;
+}
+
+uint64_t bits_of(double x) {
+  uint64_t u;
+  memcpy(&u, &x, 8);
+  return u;
+}
+
+struct Span {
+  uintptr_t b, e;
+};
+
+// some output [b, e) shares a byte with some input
+bool outputs_meet_inputs(std::vector<Span> ins, const std::vector<Span>& outs) {
+  std::sort(ins.begin(), ins.end(), [](const Span& x, const Span& y) { return x.b < y.b; });
+  std::vector<uintptr_t> reach(ins.size());  // the furthest end among the inputs up to this one
+  for (size_t i = 0; i < ins.size(); i++) reach[i] = std::max(ins[i].e, i ? reach[i - 1] : 0);
+  for (const Span& o : outs) {
+    const size_t k = std::lower_bound(ins.begin(), ins.end(), o.e, [](const Span& x, uintptr_t v) { return x.b < v; }) - ins.begin();
+    if (k > 0 && reach[k - 1] > o.b) return true;  // (the inputs that begin before the output's end)
+  }
+  return false;
+}
+
+// What a call brings: the list, and this rank's slices of it on p ranks
+struct Call {
+  const void* const* ins;
+  void* const* outs;
+  const int64_t *rows, *row_elems;
+  int n, dtype, es;
+  tips::Scale sc;
+};
+
+const char* slice_of(const Call& c, int i, int p, int q, int64_t* elems) {
+  int64_t begin;
+  *elems = tips::rs_rows(c.rows[i], p, q, &begin) * c.row_elems[i];
+  return (const char*)c.ins[i] + begin * c.row_elems[i] * c.es;
+}
+
+// this rank's verdict on its pointers (device memory, element-aligned, no output over an input)
+int check_pointers(const Call& c, int p, int rank) {
+  if (!c.ins || !c.outs) return fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  std::vector<Span> ins, outs;
+  for (int i = 0; i < c.n; i++) {
+    const int64_t bytes = c.rows[i] * c.row_elems[i] * c.es;
+    if (bytes == 0) continue;
+    TRY(need_device(c.ins[i], "an input", kTakes));
+    const uintptr_t a = reinterpret_cast<uintptr_t>(c.ins[i]);
+    if (a & (uintptr_t)(c.es - 1)) return fail(TIPS_ERR_INVALID_ARG, "input %d is not %d-B aligned", i, c.es);
+    ins.push_back(Span{a, a + (uintptr_t)bytes});
+    int64_t own;
+    slice_of(c, i, p, rank, &own);
+    if (own == 0) continue;
+    TRY(need_device(c.outs[i], "an output", kTakes));
+    const uintptr_t o = reinterpret_cast<uintptr_t>(c.outs[i]);
+    if (o & (uintptr_t)(c.es - 1)) return fail(TIPS_ERR_INVALID_ARG, "output %d is not %d-B aligned", i, c.es);
+    outs.push_back(Span{o, o + (uintptr_t)(own * c.es)});
+  }
+  if (outputs_meet_inputs(ins, outs)) return fail(TIPS_ERR_INVALID_ARG, "an output overlaps an input (the reduce-scatter is out of place)");
+  return 0;
+}
+
+// The schedule. Caller holds st.mu and st.rscatter.mu.
+int run_collective(State& st, const Call& c, hipStream_t s) {
+  const int p = st.size, rank = st.rank, n = c.n;
+  std::vector<int64_t> offs((size_t)n);
+  std::vector<tips::FoldSeg> segs;
+  auto region = [&](int q) { return tips::rs_layout(c.rows, c.row_elems, n, c.es, p, q, offs.data()); };
+  const int64_t slot = round_up(region(0), kAlignBytes);  // region 0 is the largest
+  const bool packed = p > 1 && n > 1;
+  TRY(st.rscatter.open(s, (size_t)((packed ? 2 : 1) * (int64_t)(p - 1) * slot)));
+  char* stage = (char*)st.rscatter.scratch.p;  // the peers' regions `rank`, then (packed) this rank's regions for them
+  char* send = stage + (int64_t)(p - 1) * slot;
+  auto slot_of = [&](char* base, int r) { return base + (int64_t)(r < rank ? r : r - 1) * slot; };
+  std::vector<int64_t> bytes_of((size_t)p);
+  for (int q = 0; q < p; q++) bytes_of[q] = region(q);
+  if (p > 1) {
+    TRY(ensure_comm(st));
+    if (packed) {
+      // the pack: the kernel's one-source form, the peers' send slots laid end to end as its byte space
+      for (int q = 0; q < p; q++) {
+        if (q == rank || bytes_of[q] == 0) continue;
+        region(q);
+        char* to = slot_of(send, q);
+        for (int i = 0; i < n; i++) {
+          int64_t elems;
+          const char* from = slice_of(c, i, p, q, &elems);
+          if (elems > 0) segs.push_back(tips::FoldSeg{from, to + offs[i], (int64_t)(to - send) + offs[i], elems});
+        }
+      }
+      HIP_TRY(tips::launch_fold_segs(segs.data(), (int)segs.size(), nullptr, 1, 0, c.dtype, tips::Scale(), s));
+      segs.clear();
+    }
+    TRY(rccl_enter(st, s));
+    NCCL_TRY(ncclGroupStart());
+    for (int q = 0; q < p; q++) {
+      if (q == rank) continue;
+      if (bytes_of[q] > 0) {
+        int64_t elems;
+        const void* from = packed ? slot_of(send, q) : slice_of(c, 0, p, q, &elems);
+        NCCL_TRY(ncclSend(from, (size_t)bytes_of[q], ncclInt8, q, st.comm, s));
+      }
+      if (bytes_of[rank] > 0) NCCL_TRY(ncclRecv(slot_of(stage, q), (size_t)bytes_of[rank], ncclInt8, q, st.comm, s));
+    }
+    NCCL_TRY(ncclGroupEnd());
+    TRY(rccl_leave(st, s));
+  }
+  if (bytes_of[rank] > 0) {
+    region(rank);
+    for (int i = 0; i < n; i++) {
+      int64_t elems;
+      const char* own = slice_of(c, i, p, rank, &elems);
+      if (elems > 0) segs.push_back(tips::FoldSeg{own, c.outs[i], offs[i], elems});
+    }
+    const void* stages[tips::kMaxSrcs] = {};
+    for (int r = 0; r < p; r++)
+      if (r != rank) stages[r] = slot_of(stage, r);
+    HIP_TRY(tips::launch_fold_segs(segs.data(), (int)segs.size(), stages, p, rank, c.dtype, c.sc, s));
+  }
+  return st.rscatter.close(s);
+}
+
+int collective(const char* what, const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
+               int n, int dtype, int op, double pre, double post, hipStream_t s) {
+  // What needs no device comes first; once the call is open it is part of this rank's verdict, so
+  // that a rank which refuses its arguments does not leave the others waiting in the exchange.
+  int64_t total = 0;
+  int own = check_op(dtype, op, pre, post);
+  if (own == 0) own = check_shapes(rows, row_elems, n, tips::dtype_size(dtype), &total);
+  if (own == 0 && n > 0 && (!ins || !outs)) own = fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  const bool usable = own == 0;  // the list can be read
+  const std::string early = own ? last_error() : std::string();
+  State& st = S();
+  std::unique_lock<std::mutex> one;
+  int size;
+  if (const int rc = side_open(st, st.rscatter, what, "reduce-scatter", at_most_max_srcs, /*rccl_only=*/true, &one, &size))
+    return own ? fail(own, "%s", early.c_str()) : rc;
+  Call c{ins, outs, rows, row_elems, n, dtype, tips::dtype_size(dtype), scale_of(op, pre, post)};
+  if (own) {
+    (void)fail(own, "%s", early.c_str());
+  } else {
+    // a capturing stream is this rank's refusal, like a pointer it does not accept
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+    else if (cs != hipStreamCaptureStatusNone)
+      own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
+    if (own == 0) {
+      int rank;
+      {
+        std::lock_guard<std::mutex> lk(st.mu);
+        rank = st.rank;
+      }
+      own = check_pointers(c, size, rank);
+    }
+  }
+  uint64_t h = kFnvBasis;
+  if (usable) {
+    std::vector<int64_t> shape((size_t)2 * n);
+    for (int i = 0; i < n; i++) shape[2 * i] = rows[i], shape[2 * i + 1] = row_elems[i];
+    h = hash_counts(shape.data(), 2 * n);
+  }
+  const int64_t mine[8] = {usable ? n : -1, total, (int64_t)h, dtype, op, (int64_t)bits_of(pre), (int64_t)bits_of(post), own};
+  SideRecords rec;
+  TRY(side_exchange(size, mine, 8, &rec));
+  // reported in this order: a mismatch, another rank's refusal, this rank's own
+  if (const int r = rec.first_differing(0, 7); r >= 0) {
+    const int64_t *q = rec.of(r), *q0 = rec.of(0);
+    return fail(TIPS_ERR_MISMATCH,
+                "Mismatched reduce-scatter: rank %d has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
+                "factor bits %llx / %llx; rank 0 has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
+                "factor bits %llx / %llx",
+                r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)q[3], (long long)q[4],
+                (unsigned long long)q[5], (unsigned long long)q[6], (long long)q0[0], (long long)q0[1],
+                (unsigned long long)q0[2], (long long)q0[3], (long long)q0[4], (unsigned long long)q0[5],
+                (unsigned long long)q0[6]);
+  }
+  if (!own)
+    if (const int r = rec.first_refusing(); r >= 0)
+      return fail(TIPS_ERR_MISMATCH, "reduce-scatter: rank %d refused its arguments (status %lld)", r, (long long)rec.of(r)[7]);
+  TRY(rec.report_own());
+  if (total == 0) return 0;
+  std::lock_guard<std::mutex> lk(st.mu);
+  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
+  TRY(set_device(st));
+  return run_collective(st, c, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t tips_reducescatter_rows(int64_t rows, int nranks, int rank, int64_t* begin) {
+  if (rows < 0 || nranks < 1 || rank < 0 || rank >= nranks)
+    return fail(TIPS_ERR_INVALID_ARG, "bad split (rows %lld, rank %d of %d)", (long long)rows, rank, nranks);
+  return tips::rs_rows(rows, nranks, rank, begin);
+}
+
+int64_t tips_reducescatter_layout(const int64_t* rows, const int64_t* row_elems, int n, int dtype, int nranks, int rank,
+                                  int64_t* offsets) {
+  TRY(check_dtype(dtype));
+  if (nranks < 1 || rank < 0 || rank >= nranks) return fail(TIPS_ERR_INVALID_ARG, "bad rank (%d of %d)", rank, nranks);
+  int64_t total;
+  TRY(check_shapes(rows, row_elems, n, tips::dtype_size(dtype), &total));
+  return tips::rs_layout(rows, row_elems, n, tips::dtype_size(dtype), nranks, rank, offsets);
+}
+
+int tips_reducescatter_fold(void* const* outs, const void* const* own, const int64_t* counts, const int64_t* offsets, int n,
+                            const void* const* stages, int nsrc, int own_pos, int dtype, int op, double prescale,
+                            double postscale, void* stream) {
+  TRY(check_op(dtype, op, prescale, postscale));
+  if (nsrc < 1 || nsrc > tips::kMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1 ... %d (got %d)", tips::kMaxSrcs, nsrc);
+  if (own_pos < 0 || own_pos >= nsrc) return fail(TIPS_ERR_INVALID_ARG, "own_pos %d is outside 0 ... %d", own_pos, nsrc - 1);
+  int64_t total;
+  TRY(check_counts(counts, n, "segment", &total));
+  if (n > 0 && (!outs || !own || !offsets)) return fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  if (nsrc > 1 && !stages) return fail(TIPS_ERR_INVALID_ARG, "null pointer (stages)");
+  const int64_t es = tips::dtype_size(dtype);
+  std::vector<tips::FoldSeg> segs;
+  int64_t end = 0;  // the region byte behind the last non-empty segment
+  for (int i = 0; i < n; i++) {
+    if (counts[i] == 0) continue;
+    if (offsets[i] < 0 || offsets[i] % kAlignBytes != 0)
+      return fail(TIPS_ERR_INVALID_ARG, "offset %lld of segment %d is not a multiple of %lld", (long long)offsets[i], i,
+                  (long long)kAlignBytes);
+    if (offsets[i] < end) return fail(TIPS_ERR_INVALID_ARG, "segment %d begins inside an earlier one (offsets ascend)", i);
+    if (!outs[i] || !own[i]) return fail(TIPS_ERR_INVALID_ARG, "null pointer (segment %d)", i);
+    if ((reinterpret_cast<uintptr_t>(outs[i]) | reinterpret_cast<uintptr_t>(own[i])) & (uintptr_t)(es - 1))
+      return fail(TIPS_ERR_INVALID_ARG, "segment %d is not %lld-B aligned", i, (long long)es);
+    end = offsets[i] + counts[i] * es;
+    segs.push_back(tips::FoldSeg{own[i], outs[i], offsets[i], counts[i]});
+  }
+  if (segs.empty()) return 0;
+  for (int j = 0; j < nsrc; j++)
+    if (j != own_pos) {
+      if (!stages[j]) return fail(TIPS_ERR_INVALID_ARG, "null pointer (stage %d)", j);
+      if (reinterpret_cast<uintptr_t>(stages[j]) & 15) return fail(TIPS_ERR_INVALID_ARG, "stage %d is not 16-B aligned", j);
+    }
+  // (like tips_multi_sum, the kernel's own entry does not probe its pointers: two lookups per segment
+  // cost a 214-segment call more than its launches)
+  HIP_TRY(tips::launch_fold_segs(segs.data(), (int)segs.size(), stages, nsrc, own_pos, dtype, scale_of(op, prescale, postscale),
+                                 (hipStream_t)stream));
+  return 0;
+}
+
+int tips_reducescatter(const void* in, void* out, int64_t rows, int64_t row_elems, int dtype, int op, double prescale,
+                       double postscale, void* stream) {
+  return collective("tips_reducescatter", &in, &out, &rows, &row_elems, 1, dtype, op, prescale, postscale, (hipStream_t)stream);
+}
+
+int tips_grouped_reducescatter(const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems, int n,
+                               int dtype, int op, double prescale, double postscale, void* stream) {
+  return collective("tips_grouped_reducescatter", ins, outs, rows, row_elems, n, dtype, op, prescale, postscale,
+                    (hipStream_t)stream);
+}
+
+}  // extern "C"

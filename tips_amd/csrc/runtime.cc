@@ -132,6 +132,7 @@ void tips_shutdown(void) {
   st.sparse.release();
   adasum_release(st);
   st.mxfp8.release();
+  st.rscatter.release();
   st.tuned.clear();
   st.recv_ev.release();
   st.sum_ev.release();

@@ -1313,3 +1313,89 @@ def set_algorithm(algo):
     prev = _lib.lib().tips_get_algorithm()
     _lib.call("tips_set_algorithm", names[algo])
     return inv.get(prev, str(prev))
+
+
+def reducescatter_rows(rows, nranks, rank):
+    """(first row, rows) rank `rank` of `nranks` owns of a [rows, ...] tensor (tips_reducescatter_rows)."""
+    import ctypes
+    begin = ctypes.c_int64()
+    own = _lib.call("tips_reducescatter_rows", int(rows), int(nranks), int(rank), ctypes.byref(begin))
+    return int(begin.value), int(own)
+
+
+def _check_reducescatter(tensor_list, op, pre, post, name):
+    """The argument checks of reducescatter / grouped_reducescatter, before anything is initialised."""
+    if name is not None:
+        raise ValueError("reducescatter takes no name: named requests go through the negotiation, which carries SUM "
+                         "allreduce only")
+    if op == "Adasum":
+        raise ValueError("op=Adasum is not defined for reducescatter")
+    if op not in ("Average", "Sum", "Max", "Min"):
+        raise ValueError("reducescatter: op must be Average, Sum, Max or Min (got %r)" % (op,))
+    scaled = pre != 1.0 or post != 1.0
+    if op in ("Max", "Min") and scaled:
+        raise ValueError("op=%s takes no prescale_factor / postscale_factor: there is no scaled Max / Min" % op)
+    for t in tensor_list:
+        if t is None:
+            continue
+        if not tensors.is_torch(t):
+            raise ValueError("reducescatter takes device torch tensors (got %s): host tensors are not staged" % type(t).__name__)
+        if t.is_sparse:
+            raise ValueError("reducescatter is not defined for sparse tensors: densify first")
+        if t.dim() == 0:
+            raise ValueError("reducescatter splits dimension 0: a 0-dim tensor has none")
+        try:
+            tensors.dtype_code(t)
+        except TypeError as e:
+            raise ValueError(str(e))
+        if _is_integer(t) and (op == "Average" or scaled):
+            raise ValueError("integer tensors (dtype %s) take no scale factor and no op=Average: reduce with op=Sum" % t.dtype)
+        if not t.is_cuda:
+            raise ValueError("reducescatter takes device tensors only (host pointers are not staged)")
+
+
+def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, postscale_factor=1.0, name=None):
+    """This rank's rows of the reduction of every tensor of the list over all ranks
+    (tips_grouped_reducescatter; DESIGN.md, Reduce-scatter): one call of the library per (dtype, device)
+    group, None entries passed through. See tips_amd.grouped_reducescatter."""
+    tensor_list = list(tensor_list)
+    pre, post = float(prescale_factor), float(postscale_factor)
+    _check_reducescatter(tensor_list, op, pre, post, name)
+    basics.init()
+    torch = tensors._torch()
+    p, r = basics.size(), basics.rank()
+    if op == "Average":
+        post = post / p
+    code_op = _REDUCE_OPS["Sum" if op == "Average" else op]
+    outs = [None] * len(tensor_list)
+    groups = {}
+    for i, t in enumerate(tensor_list):
+        if t is not None:
+            groups.setdefault((t.dtype, t.device), []).append(i)
+    for (dtype, device), members in groups.items():
+        srcs = [tensor_list[i].contiguous() for i in members]
+        rows = [int(s.shape[0]) for s in srcs]
+        row_elems = [s.numel() // s.shape[0] if s.shape[0] else _prod(s.shape[1:]) for s in srcs]
+        with torch.cuda.device(device):
+            for i, s in zip(members, srcs):
+                outs[i] = torch.empty((reducescatter_rows(s.shape[0], p, r)[1],) + tuple(s.shape[1:]), dtype=dtype,
+                                      device=device)
+            stream = tensors.stream_of(srcs[0])
+            code = tensors.dtype_code(srcs[0])
+            if len(members) == 1:
+                _lib.call("tips_reducescatter", srcs[0].data_ptr(), outs[members[0]].data_ptr(), rows[0], row_elems[0],
+                          code, code_op, pre, post, stream)
+            else:
+                pi, _k1 = _lib.ptr_array([s.data_ptr() for s in srcs])
+                po, _k2 = _lib.ptr_array([outs[i].data_ptr() for i in members])
+                pr, _k3 = _lib.i64_array(rows)
+                pe, _k4 = _lib.i64_array(row_elems)
+                _lib.call("tips_grouped_reducescatter", pi, po, pr, pe, len(members), code, code_op, pre, post, stream)
+    return outs
+
+
+def _prod(dims):
+    v = 1
+    for d in dims:
+        v *= int(d)
+    return v
