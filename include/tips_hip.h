@@ -496,6 +496,67 @@ TIPS_API int tips_grouped_reducescatter(const void* const* ins, void* const* out
                                         const int64_t* row_elems, int n, int dtype, int op, double prescale,
                                         double postscale, void* stream);
 
+/* ---- MXFP8 reduce-scatter (MXFP8 reduce-scatter) ---- */
+
+/* The reduce-scatter with the MXFP8 wire: every peer value is quantised once, the owner's own slice
+ * not at all, and the owner folds in f32. The operand is a list of n contiguous FLOAT32 device tensors
+ * [rows_i, ...] with row_elems_i, split along dimension 0 by the ROW SPLIT above.
+ *   REGION q is the list of every tensor's slice q in list order, slice i of rows_i,q * row_elems_i
+ * elements. Its flat layout is tips_fused_layout over those slice counts as TIPS_FLOAT32: every
+ * non-empty slice starts on a multiple of 64 elements; E_q flat elements, a function of (rows[],
+ * row_elems[], p, q) alone; an empty slice is an empty tensor of the list. WIRE q OF RANK r is exactly
+ * the bytes tips_mxfp8_quantize produces for rank r's slices q under that layout (payload, scale bytes
+ * and quantise rules (1)-(4) of the MXFP8 wire above).
+ *   RESULT on rank q, for tensor i and element k of its slice, at flat position f = off_i + k of region q:
+ *     y_r = x_q[i][k]                             for r == q (this rank's own float32, not quantised)
+ *     y_r = dequantise(wire q of rank r)[f]       for r != q (the MXFP8 wire's dequantise, factor 1)
+ *     acc = ((y_0 + y_1) + y_2) + ... + y_{p-1}   ranks ascending, separate IEEE f32 adds, not contracted
+ *     out = acc if (float)factor == 1, acc * (float)factor otherwise (one more f32 multiply)
+ * Every NaN is stored as 0x7FC00000. A poisoned peer block (scale byte 0xFF) makes every tensor element
+ * of that block NaN on the owner and nothing outside it; a NaN or Inf in the owner's own slice touches
+ * only its own element. The same bits on every run. One rank, and one source, quantise nothing: the
+ * result is what tips_reducescatter_fold gives with one source, TIPS_OP_SUM, prescale 1 and
+ * postscale = factor - the copy, or the scaled copy. Positions that hold no tensor element are never
+ * written. The owner's slice stays raw because only the owner ever computes its shard: there is no
+ * "same bytes on every rank" to keep, and a quantise pass and a p-th of the error are saved - so an
+ * allgather of these shards is not what tips_allreduce_mxfp8 returns. */
+
+/* Pure host: E_rank, the flat elements of region `rank`; offsets[i] (offsets may be NULL) = the flat
+ * element offset of tensor i's slice (0 for an empty slice). < 0 = error. */
+TIPS_API int64_t tips_reducescatter_mxfp8_layout(const int64_t* rows, const int64_t* row_elems, int n, int nranks, int rank,
+                                                 int64_t* offsets);
+/* The kernel alone: stream-ordered, no communication, no tips_init needed. The layout is
+ * tips_fused_layout(counts, n, TIPS_FLOAT32); outs[i][k] for k < counts[i] is the RESULT above over
+ * sources j < nsrc, where source own_pos is own[i] and source j != own_pos is the 16-B aligned wire
+ * buffer wires[j] of that layout (wires[own_pos] is ignored; wires may be NULL when nsrc is 1). nsrc
+ * outside 1 ... 16, own_pos outside 0 ... nsrc - 1, negative counts, a null pointer of a non-empty
+ * tensor, a tensor that is not 4-B aligned, a wire that is null or not 16-B aligned and a factor that
+ * is not a finite float return TIPS_ERR_INVALID_ARG. A total of 0 elements is TIPS_OK with nothing
+ * launched. Like tips_reducescatter_fold it does not probe its pointers. Outputs must overlap neither
+ * the own slices nor the wires. */
+TIPS_API int tips_reducescatter_mxfp8_fold(void* const* outs, const void* const* own, const int64_t* counts, int n,
+                                           const void* const* wires, int nsrc, int own_pos, double factor, void* stream);
+/* The collective over one tensor, out of place, ordered on the caller's stream. The ranks first compare
+ * {tensors, elements, a hash of the (rows, row_elems) list with the call kind folded in, the factor's
+ * float bits} on the host, in a record of the plain reduce-scatter's length: a difference - a call
+ * paired with tips_reducescatter / tips_grouped_reducescatter on another rank included - returns
+ * TIPS_ERR_MISMATCH ("Mismatched MXFP8 reduce-scatter ...") on every rank before any device exchange.
+ * This rank's verdict on its own arguments (the checks of tips_reducescatter: sizes, a host pointer,
+ * alignment, an output over an input, a capturing stream, and the factor) travels in that record, so
+ * the other ranks return TIPS_ERR_MISMATCH "refused its arguments" and nobody waits. Then the slices of
+ * the p - 1 peer regions are quantised into runtime scratch (the own region is not), one RCCL group
+ * sends region q's payload and scale bytes to rank q and receives every peer's region `rank`
+ * (regions of no block are skipped on both sides), and the fold-dequantise writes `out`. More than 16
+ * ranks, TIPS_ALGO_PEER and a running negotiation return TIPS_ERR_UNSUPPORTED. A total of 0 elements
+ * returns after the record exchange; a rank that owns no row takes part in the exchange and launches
+ * nothing. One rank: the (scaled) copy. */
+TIPS_API int tips_reducescatter_mxfp8(const void* in, void* out, int64_t rows, int64_t row_elems, double factor,
+                                      void* stream);
+/* The collective over a list of n FLOAT32 tensors: one quantise over the peers' slices (a launch per
+ * 48 of them), one RCCL group, one fold launch per 80 output tensors. The same checks and refusals. */
+TIPS_API int tips_grouped_reducescatter_mxfp8(const void* const* ins, void* const* outs, const int64_t* rows,
+                                              const int64_t* row_elems, int n, double factor, void* stream);
+
 /* ---- control plane: cross-rank request validation ---- */
 
 /* request types = message::RequestType (collective_messages.fbs:3-7) */

@@ -18,6 +18,7 @@ from .ops import adasum_op, fused_adasum_flat
 from .ops import (allreduce_mxfp8, fused_allreduce_mxfp8, mxfp8_dequantize, mxfp8_fold, mxfp8_quantize,
                   mxfp8_wire_bytes)
 from .ops import allreduce_mxfp8_ef, fused_allreduce_mxfp8_ef, mxfp8_ef_bytes, mxfp8_fold_ef, mxfp8_quantize_ef
+from .ops import mxfp8_fold_segs, reducescatter_mxfp8_layout
 from ._lib import TipsError, TipsLibraryError
 from . import ops as _ops
 from . import tensors as _tensors
@@ -54,10 +55,11 @@ __all__ = [
     "MXFP8ErrorFeedback", "allreduce_mxfp8_ef", "fused_allreduce_mxfp8_ef", "mxfp8_ef_bytes", "mxfp8_fold_ef",
     "mxfp8_quantize_ef",
     "reducescatter", "grouped_reducescatter",
+    "reducescatter_mxfp8_layout", "mxfp8_fold_segs",
 ]
 
 
-def reducescatter(tensor, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None):
+def reducescatter(tensor, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None, compression=Compression.none):
     """This rank's rows of the reduction of `tensor` over all ranks (Horovod's reducescatter;
     tips_reducescatter; DESIGN.md, Reduce-scatter).
 
@@ -73,16 +75,45 @@ def reducescatter(tensor, op=Average, prescale_factor=1.0, postscale_factor=1.0,
     of float32, float64, float16, bfloat16, int32 or int64; the same op, factors and shape on every
     rank. ValueError, before anything is initialised, for a 0-dim, host or sparse tensor, an integer
     dtype with op=Average or a factor, op=Max / Min with a factor, op=Adasum, and a `name` (named
-    requests carry SUM allreduce only)."""
-    return _ops.grouped_reducescatter_op([tensor], op, prescale_factor, postscale_factor, name)[0]
+    requests carry SUM allreduce only).
+
+    compression=Compression.fp8 sends a float32 tensor through the MXFP8 reduce-scatter
+    (tips_reducescatter_mxfp8): every peer's slice travels as e4m3fn bytes with one
+    power-of-two scale per 32 elements, quantised once; this rank's own slice is not quantised; the
+    fold is in f32 in rank order, times the one factor prescale_factor * postscale_factor (divided by
+    size() for Average) - a quarter of the plain reduce-scatter's bytes on the links. Tensors of every
+    other dtype travel uncompressed. ValueError for op=Max / Min with it, and for an MXFP8ErrorFeedback
+    object: error feedback for the reduce-scatter is not implemented. Any other compressor
+    (Compression.fp16) composes as for allreduce: compress, reduce-scatter in the compressed dtype,
+    decompress."""
+    return _reducescatter_compressed([tensor], op, prescale_factor, postscale_factor, name, compression)[0]
 
 
-def grouped_reducescatter(tensors, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None):
+def grouped_reducescatter(tensors, op=Average, prescale_factor=1.0, postscale_factor=1.0, name=None,
+                          compression=Compression.none):
     """reducescatter of every tensor of a list, one exchange and one fold launch per (dtype, device)
     group (tips_grouped_reducescatter): rank q receives every tensor's slice q in one RCCL group and
     the fold writes the outputs straight from the staged bytes. Returns the list of this rank's
-    shards; None entries pass through. Arguments and refusals as reducescatter."""
-    return _ops.grouped_reducescatter_op(tensors, op, prescale_factor, postscale_factor, name)
+    shards; None entries pass through. Arguments and refusals as reducescatter; under
+    compression=Compression.fp8 every (float32, device) group is one tips_grouped_reducescatter_mxfp8."""
+    return _reducescatter_compressed(tensors, op, prescale_factor, postscale_factor, name, compression)
+
+
+def _reducescatter_compressed(tensors, op, prescale_factor, postscale_factor, name, compression):
+    if _is_ef(compression):
+        raise ValueError("reducescatter takes no MXFP8ErrorFeedback: error feedback for the reduce-scatter's wire is not "
+                         "implemented (use Compression.fp8)")
+    if compression is MXFP8Compressor:
+        if op in (Max, Min):
+            raise ValueError("op=%s does not combine with Compression.fp8: the MXFP8 wire carries SUM (and Average) only" % op)
+        return _ops.grouped_reducescatter_op(tensors, op, prescale_factor, postscale_factor, name, mxfp8=True)
+    if compression is NoneCompressor:
+        return _ops.grouped_reducescatter_op(tensors, op, prescale_factor, postscale_factor, name)
+    tensors = list(tensors)
+    _ops._check_reducescatter(tensors, op, float(prescale_factor), float(postscale_factor), name)
+    packed = [(None, None) if t is None else compression.compress(t) for t in tensors]
+    outs = _ops.grouped_reducescatter_op([c for c, _ in packed], op, prescale_factor, postscale_factor, name)
+    return [None if o is None else compression.decompress(o, ctx) for o, (_, ctx) in zip(outs, packed)]
 
 
 def allreduce_scaled(tensor, prescale_factor=1.0, postscale_factor=1.0, name=None):

@@ -143,6 +143,15 @@ _SIGNATURES = [
     ("tips_grouped_reducescatter", ctypes.c_int,
      [_c_void_pp, _c_void_pp, _c_i64_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
       ctypes.c_double, ctypes.c_void_p]),
+    ("tips_reducescatter_mxfp8_layout", ctypes.c_int64,
+     [_c_i64_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i64_p]),
+    ("tips_reducescatter_mxfp8_fold", ctypes.c_int,
+     [_c_void_pp, _c_void_pp, _c_i64_p, ctypes.c_int, _c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+      ctypes.c_void_p]),
+    ("tips_reducescatter_mxfp8", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p]),
+    ("tips_grouped_reducescatter_mxfp8", ctypes.c_int,
+     [_c_void_pp, _c_void_pp, _c_i64_p, _c_i64_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]),
     ("tips_check_requests", ctypes.c_int, [_c_i64_p, ctypes.c_int]),
     ("tips_allreduce_checked", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, _c_i64_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),

@@ -56,4 +56,24 @@ hipError_t launch_mxfp8_fold_ef(unsigned char* dst_payload, unsigned char* dst_s
 hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,
                                    float factor, hipStream_t s);
 
+// One output tensor of the MXFP8 reduce-scatter's fold: `count` f32 elements at `dst`
+// (4-B aligned) folded from `own` (this rank's slice, 4-B aligned, not quantised) and, for every other
+// source, from the flat elements [off, off + count) of its wire buffer (off a multiple of 64).
+// Segments ascend by off and do not overlap.
+struct MxFoldSeg {
+  const void* own;
+  void* dst;
+  int64_t off, count;
+};
+// By value, like MxSeg lists; 80 records, their tile starts and the 32 source pointers keep the
+// arguments under 4 KiB with room for the launch's hidden ones (config 5's 214 gradients: 3 launches).
+constexpr int kMxFoldSegsPerLaunch = 80;
+// For every segment and element k at flat position f = off + k: dst[k] = ((y_0 + y_1) + ...) + y_{nsrc-1},
+// y_own_pos = own[k] and y_j = dequantise(wire j)[f] otherwise (wires.payload[j] / wires.scales[j]: a
+// whole wire buffer's first payload and first scale byte; entry own_pos is not read), separate f32
+// adds, then * factor when factor != 1; every NaN stored as 0x7FC00000. One source: reducescatter.hip's
+// copy (factor 1, every bit kept) or scaled copy.
+hipError_t launch_mxfp8_fold_segs(const MxFoldSeg* segs, int nseg, const MxSrcs& wires, int nsrc, int own_pos, float factor,
+                                  hipStream_t s);
+
 }  // namespace tips

@@ -28,14 +28,20 @@
 // v_cvt_scalef32_pk_fp8_f32 is not used: it does not saturate (a quotient above 448 becomes 0x7F)
 // and its result under the scale 2^-127 differs from the definition.
 //
+// The reduce-scatter's fold-dequantise (defined where its kernel is) reads the peers'
+// wire bytes and this rank's own f32 slices and writes f32 straight into a list of output tensors.
+//
 // Launch shapes. Quantise and dequantise: one workgroup of 256 lanes per tile of 4096 flat elements
 // of one segment (tensor), 4 rounds of 4 elements per lane - a 16-B load (store) per lane and round
 // where the tensor's address is 16-B aligned and the 4 elements lie inside it, element by element
 // otherwise, into the same lanes: the same bits. 8 lanes make a block; its maximum takes three
 // cross-lane steps inside a row (DPP). Each lane stores its 4 payload bytes as one dword; the block's
 // first lane stores the scale byte. Fold: 16 payload bytes per lane and source, two lanes per block.
+#include <vector>
+
 #include "kernels_device.h"
 #include "mxfp8.h"
+#include "reducescatter.h"
 
 namespace tips {
 
@@ -99,8 +105,9 @@ __device__ __forceinline__ float scale_value(unsigned sb) {
   return __builtin_bit_cast(float, sb == 255u ? kQuietNaN : (sb ? (sb << 23) : 0x00400000u));
 }
 
-// the segment that tile t of the launch belongs to
-__device__ __forceinline__ int seg_of_tile(const MxSegList& L, int64_t t) {
+// the segment that tile t of the launch belongs to (MxSegList, MxFoldList)
+template <class List>
+__device__ __forceinline__ int seg_of_tile(const List& L, int64_t t) {
   int lo = 0, hi = L.nseg - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -402,6 +409,96 @@ __global__ __launch_bounds__(kBlock) void mxfp8_dequantize_kernel(MxSegList L, c
   }
 }
 
+// ---- the reduce-scatter's fold-dequantise ----
+//
+// mxfp8_dequantize_kernel's launch shape over the output tensors of one region: a workgroup per tile
+// of 4096 elements of one segment, 4 rounds of 4 elements per lane. Per round a lane loads its 4 own
+// elements (one 16-B nontemporal load where `own` is 16-B aligned and the 4 elements lie inside the
+// segment, element by element otherwise) and, per peer, one payload dword and the block's scale byte
+// - all before the first add - then folds the sources in ascending order: the own slice raw, a peer
+// through the dequantise's conversion (v_cvt_scalef32_pk_f32_fp8). A payload dword of a ragged tail
+// reaches up to 3 bytes past the segment's last element: they lie inside the segment's last block,
+// which the wire buffer holds whole. Source counts 2 ... 8 have an instance each; 9 ... 16 share the
+// K = 16 instance behind a workgroup-uniform j < nsrc. One source never comes here (launch_fold_segs).
+struct MxFoldList {
+  MxFoldSeg seg[kMxFoldSegsPerLaunch];
+  int64_t tile0[kMxFoldSegsPerLaunch + 1];
+  MxSrcs srcs;
+  int nseg, nsrc, own_pos;
+};
+
+constexpr int kMxFoldExact = 8;
+
+template <int K>
+__global__ __launch_bounds__(kBlock) void mxfp8_fold_segs_kernel(MxFoldList L, float factor, int has_factor) {
+#pragma clang fp contract(off)
+  constexpr bool kExact = K <= kMxFoldExact;
+  constexpr int kUnroll = kExact ? kMxRounds : 1;
+  const int nsrc = kExact ? K : L.nsrc;
+  const int own_pos = L.own_pos;
+  const int tid = threadIdx.x;
+  const int64_t t = blockIdx.x;
+  const int si = seg_of_tile(L, t);
+  const MxFoldSeg sg = L.seg[si];
+  const int64_t base = (t - L.tile0[si]) * kMxTileElems;
+  const float* own = (const float*)sg.own;
+  float* dst = (float*)sg.dst;
+  const bool vec_own = (reinterpret_cast<uintptr_t>(own) & 15) == 0, vec_dst = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  // (the K = 16 instance keeps its rounds apart: unrolled, their loads would take every register)
+#pragma unroll kUnroll
+  for (int u = 0; u < kMxRounds; u++) {
+    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
+    if (i0 >= sg.count) continue;
+    const bool full = i0 + 4 <= sg.count;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (vec_own && full) {
+      x = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(own + i0)));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) x[j] = own[i0 + j];
+    }
+    unsigned w[K], sb[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      w[j] = 0, sb[j] = 0;
+      if ((kExact || j < nsrc) && j != own_pos) {
+        w[j] = *(const unsigned*)(L.srcs.payload[j] + sg.off + i0);
+        sb[j] = L.srcs.scales[j][(sg.off + i0) >> 5];
+      }
+    }
+    f32x4 acc = x;  // (own_pos == 0; otherwise replaced by source 0 below)
+#pragma unroll
+    for (int j = 0; j < K; j++)
+      if (kExact || j < nsrc) {
+        f32x4 y = x;
+        if (j != own_pos) {
+          const float scale = scale_value(sb[j]);
+          const f32x2 lo = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((int)w[j], scale, false);
+          const f32x2 hi = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((int)w[j], scale, true);
+          y = f32x4{lo[0], lo[1], hi[0], hi[1]};
+        }
+        acc = j == 0 ? y : acc + y;
+      }
+    if (has_factor) acc = acc * factor;
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = canonical(acc[j]);
+    if (vec_dst && full) {
+      st16<false>((u32x4*)(dst + i0), __builtin_bit_cast(u32x4, acc));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (i0 + j < sg.count) dst[i0 + j] = acc[j];
+    }
+  }
+}
+
+template <int K>
+hipError_t run_fold_segs(const MxFoldList& L, unsigned tiles, float factor, hipStream_t s) {
+  hipLaunchKernelGGL(mxfp8_fold_segs_kernel<K>, dim3(tiles), dim3(kBlock), 0, s, L, factor, factor != 1.0f ? 1 : 0);
+  return hipGetLastError();
+}
+
 // the launches of a segment list, kMxSegsPerLaunch segments at a time; launch(list, tiles) per part
 template <class F>
 hipError_t for_each_part(const MxSeg* segs, int nseg, bool by_span, F launch) {
@@ -481,6 +578,49 @@ hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned c
                        factor != 1.0f ? 1 : 0);
     return hipGetLastError();
   });
+}
+
+hipError_t launch_mxfp8_fold_segs(const MxFoldSeg* segs, int nseg, const MxSrcs& wires, int nsrc, int own_pos, float factor,
+                                  hipStream_t s) {
+  if (nseg < 0 || (nseg > 0 && !segs) || nsrc < 1 || nsrc > kMxMaxSrcs || own_pos < 0 || own_pos >= nsrc)
+    return hipErrorInvalidValue;
+  if (nsrc == 1) {  // no peer, nothing quantised: the reduce-scatter's one-source fold, the (scaled) copy
+    std::vector<FoldSeg> plain;
+    for (int i = 0; i < nseg; i++)
+      if (segs[i].count > 0) plain.push_back(FoldSeg{segs[i].own, segs[i].dst, segs[i].off * 4, segs[i].count});
+    Scale sc;
+    sc.post = factor;
+    return launch_fold_segs(plain.data(), (int)plain.size(), nullptr, 1, 0, kF32, sc, s);
+  }
+  MxFoldList L;
+  L.srcs = wires;
+  L.nsrc = nsrc;
+  L.own_pos = own_pos;
+  int i = 0;
+  while (i < nseg) {
+    L.nseg = 0;
+    int64_t tiles = 0;
+    for (; i < nseg && L.nseg < kMxFoldSegsPerLaunch; i++) {
+      if (segs[i].count <= 0) continue;
+      L.seg[L.nseg] = segs[i];
+      L.tile0[L.nseg++] = tiles;
+      tiles += (segs[i].count + kMxTileElems - 1) / kMxTileElems;
+    }
+    if (!L.nseg) break;
+    L.tile0[L.nseg] = tiles;
+    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
+    hipError_t err;
+    switch (nsrc) {
+#define TIPS_MX_FOLD_SEGS_CASE(K) \
+  case K: err = run_fold_segs<K>(L, (unsigned)tiles, factor, s); break;
+      TIPS_MX_FOLD_SEGS_CASE(2) TIPS_MX_FOLD_SEGS_CASE(3) TIPS_MX_FOLD_SEGS_CASE(4) TIPS_MX_FOLD_SEGS_CASE(5)
+      TIPS_MX_FOLD_SEGS_CASE(6) TIPS_MX_FOLD_SEGS_CASE(7) TIPS_MX_FOLD_SEGS_CASE(8)
+#undef TIPS_MX_FOLD_SEGS_CASE
+      default: err = run_fold_segs<kMxMaxSrcs>(L, (unsigned)tiles, factor, s);
+    }
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
 }
 
 }  // namespace tips

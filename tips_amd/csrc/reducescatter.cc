@@ -4,12 +4,18 @@
 // rank q in one RCCL group and folds the p sources of its own slices in rank order, straight into the
 // callers' outputs. It is the direct schedule's first half: the same fold over the same operands, so a
 // shard is bit-identical to that slice of the direct allreduce.
+// The MXFP8 reduce-scatter (tips_reducescatter_mxfp8_layout, tips_reducescatter_mxfp8_fold,
+// tips_reducescatter_mxfp8, tips_grouped_reducescatter_mxfp8) is the same exchange with the peer
+// regions quantised once (mxfp8.hip's quantise) and the owner's fold reading wire bytes beside its
+// own f32 slices (mxfp8.hip's fold-dequantise).
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
+#include "mxfp8.h"
 #include "reducescatter.h"
 #include "rt.h"
 #include "side.h"
@@ -244,6 +250,194 @@ int collective(const char* what, const void* const* ins, void* const* outs, cons
   return run_collective(st, c, s);
 }
 
+// ---- the MXFP8 reduce-scatter ----
+
+int check_factor(double factor) {
+  if (!isfinite(factor) || !isfinite((float)factor)) return fail(TIPS_ERR_INVALID_ARG, "factor %g is not a finite float", factor);
+  return 0;
+}
+
+uint32_t float_bits_of(double x) {
+  const float f = (float)x;
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
+// Region q of a list as the MXFP8 wire sees it: the slices' element counts, their flat element
+// offsets under tips_fused_layout(counts, n, FLOAT32) and the flat element count E_q
+struct MxRegion {
+  std::vector<int64_t> counts, offs;
+  int64_t elems = 0;
+};
+
+MxRegion mx_region(const int64_t* rows, const int64_t* row_elems, int n, int p, int q) {
+  MxRegion r;
+  r.counts.resize((size_t)n);
+  r.offs.assign((size_t)n, 0);
+  int64_t total = 0;
+  for (int i = 0; i < n; i++) total += r.counts[i] = tips::rs_rows(rows[i], p, q, nullptr) * row_elems[i];
+  if (total > 0) {
+    r.elems = fused_layout(r.counts.data(), n, TIPS_FLOAT32, r.offs.data()) / 4;
+    for (int i = 0; i < n; i++) r.offs[i] /= 4;
+  }
+  return r;
+}
+
+// the order the kernels want: ascending flat offset (the layout puts a tensor of at least the fusion
+// threshold behind the others, whatever its place in the list)
+std::vector<int> by_offset(const MxRegion& r) {
+  std::vector<int> idx;
+  for (int i = 0; i < (int)r.counts.size(); i++)
+    if (r.counts[i] > 0) idx.push_back(i);
+  std::sort(idx.begin(), idx.end(), [&](int a, int b) { return r.offs[a] < r.offs[b]; });
+  return idx;
+}
+
+tips::MxSrcs wires_of(const void* const* wires, int nsrc, int own_pos, int64_t elems) {
+  tips::MxSrcs w = {};
+  for (int j = 0; j < nsrc; j++)
+    if (j != own_pos) {
+      w.payload[j] = (const unsigned char*)wires[j];
+      w.scales[j] = w.payload[j] + tips::mxfp8_scales_offset(elems);
+    }
+  return w;
+}
+
+// The schedule. Caller holds st.mu and st.rscatter.mu.
+int run_mx_collective(State& st, const Call& c, double factor, hipStream_t s) {
+  const int p = st.size, rank = st.rank, n = c.n;
+  std::vector<MxRegion> reg;
+  for (int q = 0; q < p; q++) reg.push_back(mx_region(c.rows, c.row_elems, n, p, q));
+  const MxRegion& mine = reg[rank];
+  // The send buffer is one wire buffer over the peers' regions laid end to end, each from a multiple
+  // of 256 flat elements: region q's payload and scale bytes are then exactly its own wire buffer's,
+  // at payload byte base[q] and scale byte base[q] / 32, and one quantise (a launch per 48 slices) fills it.
+  std::vector<int64_t> base((size_t)p, 0);
+  int64_t send_elems = 0;
+  for (int q = 0; q < p; q++)
+    if (q != rank) base[q] = send_elems, send_elems += tips::mxfp8_scales_offset(reg[q].elems);
+  const int64_t send_bytes = send_elems ? tips::mxfp8_wire_bytes(send_elems) : 0;
+  const int64_t slot = p > 1 ? tips::mxfp8_wire_bytes(mine.elems) : 0;  // a peer's region `rank`: a whole wire buffer
+  TRY(st.rscatter.open(s, (size_t)(send_bytes + (int64_t)(p - 1) * slot)));
+  unsigned char* send = (unsigned char*)st.rscatter.scratch.p;
+  unsigned char* stage = send + send_bytes;
+  auto slot_of = [&](int r) { return stage + (int64_t)(r < rank ? r : r - 1) * slot; };
+  if (p > 1) {
+    TRY(ensure_comm(st));
+    if (send_elems > 0) {
+      std::vector<tips::MxSeg> segs;
+      for (int q = 0; q < p; q++) {
+        if (q == rank) continue;
+        for (int i : by_offset(reg[q])) {
+          int64_t elems;
+          const char* from = slice_of(c, i, p, q, &elems);
+          segs.push_back(tips::MxSeg{from, base[q] + reg[q].offs[i], elems, 0});
+        }
+      }
+      for (size_t i = 0; i < segs.size(); i++)  // a segment covers the padding up to the next one
+        segs[i].span = (i + 1 < segs.size() ? segs[i + 1].off : send_elems) - segs[i].off;
+      if (segs[0].off > 0) segs.insert(segs.begin(), tips::MxSeg{nullptr, 0, 0, segs[0].off});
+      HIP_TRY(tips::launch_mxfp8_quantize(segs.data(), (int)segs.size(), send, send + send_elems, send_elems / tips::kMxBlock,
+                                          send_bytes - send_elems, s));
+    }
+    const int64_t in_blocks = tips::mxfp8_blocks(mine.elems);
+    TRY(rccl_enter(st, s));
+    NCCL_TRY(ncclGroupStart());
+    for (int q = 0; q < p; q++) {
+      if (q == rank) continue;
+      if (const int64_t b = tips::mxfp8_blocks(reg[q].elems); b > 0) {
+        NCCL_TRY(ncclSend(send + base[q], (size_t)(b * tips::kMxBlock), ncclInt8, q, st.comm, s));
+        NCCL_TRY(ncclSend(send + send_elems + base[q] / tips::kMxBlock, (size_t)b, ncclInt8, q, st.comm, s));
+      }
+      if (in_blocks > 0) {
+        NCCL_TRY(ncclRecv(slot_of(q), (size_t)(in_blocks * tips::kMxBlock), ncclInt8, q, st.comm, s));
+        NCCL_TRY(ncclRecv(slot_of(q) + tips::mxfp8_scales_offset(mine.elems), (size_t)in_blocks, ncclInt8, q, st.comm, s));
+      }
+    }
+    NCCL_TRY(ncclGroupEnd());
+    TRY(rccl_leave(st, s));
+  }
+  if (mine.elems > 0) {
+    std::vector<tips::MxFoldSeg> segs;
+    for (int i : by_offset(mine)) {
+      int64_t elems;
+      const char* own = slice_of(c, i, p, rank, &elems);
+      segs.push_back(tips::MxFoldSeg{own, c.outs[i], mine.offs[i], elems});
+    }
+    const void* slots[tips::kMxMaxSrcs] = {};
+    for (int r = 0; r < p; r++)
+      if (r != rank) slots[r] = slot_of(r);
+    HIP_TRY(tips::launch_mxfp8_fold_segs(segs.data(), (int)segs.size(), wires_of(slots, p, rank, mine.elems), p, rank,
+                                         (float)factor, s));
+  }
+  return st.rscatter.close(s);
+}
+
+int mx_collective(const char* what, const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
+                  int n, double factor, hipStream_t s) {
+  // as collective() above: what needs no device first, then part of this rank's verdict
+  int64_t total = 0;
+  int own = check_factor(factor);
+  if (own == 0) own = check_shapes(rows, row_elems, n, 4, &total);
+  if (own == 0 && n > 0 && (!ins || !outs)) own = fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  const bool usable = own == 0;
+  const std::string early = own ? last_error() : std::string();
+  State& st = S();
+  std::unique_lock<std::mutex> one;
+  int size;
+  if (const int rc = side_open(st, st.rscatter, what, "MXFP8 reduce-scatter", at_most_max_srcs, /*rccl_only=*/true, &one, &size))
+    return own ? fail(own, "%s", early.c_str()) : rc;
+  Call c{ins, outs, rows, row_elems, n, TIPS_FLOAT32, 4, tips::Scale()};
+  if (own) {
+    (void)fail(own, "%s", early.c_str());
+  } else {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+    else if (cs != hipStreamCaptureStatusNone)
+      own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
+    if (own == 0) {
+      int rank;
+      {
+        std::lock_guard<std::mutex> lk(st.mu);
+        rank = st.rank;
+      }
+      own = check_pointers(c, size, rank);
+    }
+  }
+  // The record has the plain reduce-scatter's eight words, so that a call paired with
+  // tips_reducescatter / tips_grouped_reducescatter on another rank is a mismatch there and here: the
+  // call kind is folded into the shape hash, the factor's float bits stand where the prescale's do.
+  uint64_t h = kFnvBasis;
+  if (usable) {
+    std::vector<int64_t> shape((size_t)2 * n);
+    for (int i = 0; i < n; i++) shape[2 * i] = rows[i], shape[2 * i + 1] = row_elems[i];
+    h = hash_counts(shape.data(), 2 * n);
+  }
+  h = (h ^ 0xF8ull) * kFnvPrime;
+  const int64_t mine[8] = {usable ? n : -1, total, (int64_t)h, TIPS_FLOAT32, TIPS_OP_SUM, (int64_t)float_bits_of(factor), 0, own};
+  SideRecords rec;
+  TRY(side_exchange(size, mine, 8, &rec));
+  if (const int r = rec.first_differing(0, 7); r >= 0) {
+    const int64_t *q = rec.of(r), *q0 = rec.of(0);
+    return fail(TIPS_ERR_MISMATCH,
+                "Mismatched MXFP8 reduce-scatter: rank %d has %lld tensors, %lld elements, call and shape hash %llx, factor bits "
+                "%llx; rank 0 has %lld tensors, %lld elements, call and shape hash %llx, factor bits %llx",
+                r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (unsigned long long)q[5], (long long)q0[0],
+                (long long)q0[1], (unsigned long long)q0[2], (unsigned long long)q0[5]);
+  }
+  if (!own)
+    if (const int r = rec.first_refusing(); r >= 0)
+      return fail(TIPS_ERR_MISMATCH, "MXFP8 reduce-scatter: rank %d refused its arguments (status %lld)", r,
+                  (long long)rec.of(r)[7]);
+  TRY(rec.report_own());
+  if (total == 0) return 0;
+  std::lock_guard<std::mutex> lk(st.mu);
+  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
+  TRY(set_device(st));
+  return run_mx_collective(st, c, factor, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -310,6 +504,59 @@ int tips_grouped_reducescatter(const void* const* ins, void* const* outs, const 
                                int dtype, int op, double prescale, double postscale, void* stream) {
   return collective("tips_grouped_reducescatter", ins, outs, rows, row_elems, n, dtype, op, prescale, postscale,
                     (hipStream_t)stream);
+}
+
+int64_t tips_reducescatter_mxfp8_layout(const int64_t* rows, const int64_t* row_elems, int n, int nranks, int rank,
+                                        int64_t* offsets) {
+  if (nranks < 1 || rank < 0 || rank >= nranks) return fail(TIPS_ERR_INVALID_ARG, "bad rank (%d of %d)", rank, nranks);
+  int64_t total;
+  TRY(check_shapes(rows, row_elems, n, 4, &total));
+  const MxRegion r = mx_region(rows, row_elems, n, nranks, rank);
+  if (offsets) std::copy(r.offs.begin(), r.offs.end(), offsets);
+  return r.elems;
+}
+
+int tips_reducescatter_mxfp8_fold(void* const* outs, const void* const* own, const int64_t* counts, int n,
+                                  const void* const* wires, int nsrc, int own_pos, double factor, void* stream) {
+  TRY(check_factor(factor));
+  if (nsrc < 1 || nsrc > tips::kMxMaxSrcs) return fail(TIPS_ERR_INVALID_ARG, "nsrc must be 1 ... %d (got %d)", tips::kMxMaxSrcs, nsrc);
+  if (own_pos < 0 || own_pos >= nsrc) return fail(TIPS_ERR_INVALID_ARG, "own_pos %d is outside 0 ... %d", own_pos, nsrc - 1);
+  int64_t total;
+  TRY(check_counts(counts, n, "tensor", &total));
+  if (n > 0 && (!outs || !own)) return fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  if (nsrc > 1 && !wires) return fail(TIPS_ERR_INVALID_ARG, "null pointer (wires)");
+  for (int i = 0; i < n; i++) {
+    if (counts[i] == 0) continue;
+    if (!outs[i] || !own[i]) return fail(TIPS_ERR_INVALID_ARG, "null pointer (tensor %d)", i);
+    if ((reinterpret_cast<uintptr_t>(outs[i]) | reinterpret_cast<uintptr_t>(own[i])) & 3)
+      return fail(TIPS_ERR_INVALID_ARG, "tensor %d is not 4-B aligned", i);
+  }
+  if (total == 0) return 0;
+  for (int j = 0; j < nsrc; j++)
+    if (j != own_pos) {
+      if (!wires[j]) return fail(TIPS_ERR_INVALID_ARG, "null pointer (wire %d)", j);
+      if (reinterpret_cast<uintptr_t>(wires[j]) & 15) return fail(TIPS_ERR_INVALID_ARG, "wire %d is not 16-B aligned", j);
+    }
+  MxRegion r;
+  r.counts.assign(counts, counts + n);
+  r.offs.assign((size_t)n, 0);
+  r.elems = fused_layout(counts, n, TIPS_FLOAT32, r.offs.data()) / 4;
+  for (int i = 0; i < n; i++) r.offs[i] /= 4;
+  std::vector<tips::MxFoldSeg> segs;
+  for (int i : by_offset(r)) segs.push_back(tips::MxFoldSeg{own[i], outs[i], r.offs[i], counts[i]});
+  // (like tips_reducescatter_fold, the kernel's own entry does not probe its pointers)
+  HIP_TRY(tips::launch_mxfp8_fold_segs(segs.data(), (int)segs.size(), wires_of(wires, nsrc, own_pos, r.elems), nsrc, own_pos,
+                                       (float)factor, (hipStream_t)stream));
+  return 0;
+}
+
+int tips_reducescatter_mxfp8(const void* in, void* out, int64_t rows, int64_t row_elems, double factor, void* stream) {
+  return mx_collective("tips_reducescatter_mxfp8", &in, &out, &rows, &row_elems, 1, factor, (hipStream_t)stream);
+}
+
+int tips_grouped_reducescatter_mxfp8(const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
+                                     int n, double factor, void* stream) {
+  return mx_collective("tips_grouped_reducescatter_mxfp8", ins, outs, rows, row_elems, n, factor, (hipStream_t)stream);
 }
 
 }  // extern "C"

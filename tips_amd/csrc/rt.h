@@ -243,6 +243,7 @@ struct State {
   SideChain adasum;  // adasum.cc: the partner's buffer, then the pair's workspace (partials and coefficients)
   SideChain mxfp8;   // mxfp8.cc: this rank's wire buffer, the reduced wire buffer and the peers' staged chunks
   SideChain rscatter;  // reducescatter.cc: the peers' staged regions, then this rank's packed regions for them
+                       // (the MXFP8 form: this rank's send wire buffer, then the peers' staged wire buffers)
   void* bounce_in = nullptr;  // page-locked kBounceBytes each (hipHostMalloc), for small pageable host tensors
   void* bounce_out = nullptr;
   HostPool* host_pool = nullptr;  // fused host tensors: pack / unpack threads

@@ -1354,13 +1354,17 @@ def _check_reducescatter(tensor_list, op, pre, post, name):
             raise ValueError("reducescatter takes device tensors only (host pointers are not staged)")
 
 
-def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, postscale_factor=1.0, name=None):
+def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, postscale_factor=1.0, name=None, mxfp8=False):
     """This rank's rows of the reduction of every tensor of the list over all ranks
     (tips_grouped_reducescatter; DESIGN.md, Reduce-scatter): one call of the library per (dtype, device)
-    group, None entries passed through. See tips_amd.grouped_reducescatter."""
+    group, None entries passed through. See tips_amd.grouped_reducescatter. `mxfp8`: every float32 group
+    goes through the MXFP8 reduce-scatter (tips_grouped_reducescatter_mxfp8) with the
+    one factor prescale * postscale; op is Average or Sum."""
     tensor_list = list(tensor_list)
     pre, post = float(prescale_factor), float(postscale_factor)
     _check_reducescatter(tensor_list, op, pre, post, name)
+    if mxfp8 and op not in ("Average", "Sum"):
+        raise ValueError("op=%s does not combine with the MXFP8 wire: it carries SUM (and Average) only" % op)
     basics.init()
     torch = tensors._torch()
     p, r = basics.size(), basics.rank()
@@ -1382,7 +1386,17 @@ def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, pos
                                       device=device)
             stream = tensors.stream_of(srcs[0])
             code = tensors.dtype_code(srcs[0])
-            if len(members) == 1:
+            if mxfp8 and dtype == torch.float32:
+                if len(members) == 1:
+                    _lib.call("tips_reducescatter_mxfp8", srcs[0].data_ptr(), outs[members[0]].data_ptr(), rows[0], row_elems[0],
+                              pre * post, stream)
+                else:
+                    pi, _k1 = _lib.ptr_array([s.data_ptr() for s in srcs])
+                    po, _k2 = _lib.ptr_array([outs[i].data_ptr() for i in members])
+                    pr, _k3 = _lib.i64_array(rows)
+                    pe, _k4 = _lib.i64_array(row_elems)
+                    _lib.call("tips_grouped_reducescatter_mxfp8", pi, po, pr, pe, len(members), pre * post, stream)
+            elif len(members) == 1:
                 _lib.call("tips_reducescatter", srcs[0].data_ptr(), outs[members[0]].data_ptr(), rows[0], row_elems[0],
                           code, code_op, pre, post, stream)
             else:
@@ -1391,6 +1405,37 @@ def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, pos
                 pr, _k3 = _lib.i64_array(rows)
                 pe, _k4 = _lib.i64_array(row_elems)
                 _lib.call("tips_grouped_reducescatter", pi, po, pr, pe, len(members), code, code_op, pre, post, stream)
+    return outs
+
+
+def reducescatter_mxfp8_layout(rows, row_elems, nranks, rank):
+    """(E, offsets) of region `rank` of the MXFP8 reduce-scatter (tips_reducescatter_mxfp8_layout; pure
+    host): the flat elements of the list of every tensor's slice `rank` under
+    tips_fused_layout, and each slice's flat element offset (0 for an empty slice)."""
+    import ctypes
+    pr, _k1 = _lib.i64_array([int(r) for r in rows])
+    pe, _k2 = _lib.i64_array([int(e) for e in row_elems])
+    offs = (ctypes.c_int64 * max(1, len(rows)))()
+    elems = _lib.call("tips_reducescatter_mxfp8_layout", pr, pe, len(rows), int(nranks), int(rank), offs)
+    return int(elems), [int(o) for o in offs[:len(rows)]]
+
+
+def mxfp8_fold_segs(outs, own, wires, own_pos, factor=1.0):
+    """The MXFP8 reduce-scatter's fold alone (tips_reducescatter_mxfp8_fold): outs[i] =
+    factor * (((y_0 + y_1) + ...) + y_{nsrc-1}) with y_own_pos = own[i], not quantised, and y_j the
+    dequantised elements of tensor i in the wire buffer wires[j] of the list's layout (mxfp8_quantize
+    of a list with own's element counts); wires[own_pos] is ignored and may be None. float32 device
+    tensors; returns outs."""
+    _check_mxfp8_list(list(outs) + list(own), "mxfp8_fold_segs")
+    if len(outs) != len(own) or any(o.numel() != w.numel() for o, w in zip(outs, own)):
+        raise ValueError("mxfp8_fold_segs: outs and own are lists of tensors of the same sizes")
+    if own:
+        po, _k1 = _lib.ptr_array([t.data_ptr() for t in outs])
+        pw, _k2 = _lib.ptr_array([t.data_ptr() for t in own])
+        pc, _k3 = _lib.i64_array([t.numel() for t in own])
+        ps, _k4 = _lib.ptr_array([0 if (j == own_pos or w is None) else w.data_ptr() for j, w in enumerate(wires)])
+        _lib.call("tips_reducescatter_mxfp8_fold", po, pw, pc, len(own), ps, len(wires), int(own_pos), float(factor),
+                  tensors.stream_of(own[0]))
     return outs
 
 
