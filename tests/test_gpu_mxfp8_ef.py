@@ -199,6 +199,48 @@ def test_fold_ef(gpu, nsrc):
     assert base.guards_kept(obuf, 4 * o0.size)
 
 
+@pytest.mark.parametrize("nsrc", [1, 2, 16])
+@pytest.mark.parametrize("nb", [1, 127, 128, 129])
+def test_fold_ef_with_a_zero_residual_is_the_plain_fold(gpu, nb, nsrc):
+    """The two fold forms share one body: over an all-zero owner residual mxfp8_fold_ef writes the payload
+    and scale bytes mxfp8_fold writes, and its new residual is the restatement's. nb blocks: less than,
+    one short of, exactly and one more than the 128 blocks of a workgroup. The sources are random wire
+    buffers: scale bytes 0 ... 240 (no product overflows), payload codes drawn from the finite codes
+    without 0x80, the two NaN codes then put at one place each - every code but 0x80, so no block sum is -0
+    (acc + +0 would turn it into +0) and every byte is compared - and one source block poisoned whole."""
+    import torch
+    elems = 32 * nb
+    nbytes, so = mx.wire_bytes(elems), mx.scales_offset(elems)
+    rng = np.random.default_rng(1000 * nb + nsrc)
+    finite = np.array([c for c in range(256) if c not in (0x7F, 0x80, 0xFF)], np.uint8)
+    wires = []
+    for j in range(nsrc):
+        w = np.zeros(nbytes, np.uint8)
+        w[:elems] = rng.choice(finite, size=elems)
+        w[rng.integers(0, elems, size=2)] = (0x7F, 0xFF)
+        w[so:so + nb] = rng.integers(0, 241, size=nb)
+        wires.append(w)
+    bad = nb // 2
+    wires[nsrc // 2][so + bad] = 255
+    wires[nsrc // 2][bad * 32:(bad + 1) * 32] = 0x7F
+    assert not any((w[:elems] == 0x80).any() for w in wires)
+    zeros = np.zeros(32 * nb, np.float32)
+    exp, exp_o = ef.fold_ef(np.full(nbytes, base.PAT, np.uint8), wires, elems, 0, nb, zeros)
+    assert exp[so + bad] == 255 and (nb == 1 or (exp[so:so + nb] != 255).any())
+    devs = [torch.from_numpy(w).cuda() for w in wires]
+    pbuf, plain = base.guarded(nbytes)
+    gpu.mxfp8_fold(plain, devs, elems, 0, nb)
+    fbuf, with_ef = base.guarded(nbytes)
+    obuf, o = guarded_f32(zeros)
+    gpu.mxfp8_fold_ef(with_ef, devs, elems, 0, nb, o)
+    torch.cuda.synchronize()
+    assert base.guards_kept(pbuf, nbytes) and base.guards_kept(fbuf, nbytes) and base.guards_kept(obuf, 4 * zeros.size)
+    assert np.array_equal(with_ef.cpu().numpy(), plain.cpu().numpy())  # every byte: payload, scales, untouched tail
+    base.same_wire(with_ef.cpu().numpy(), exp, elems)
+    same_bits(o.cpu().numpy(), exp_o, "owner residual")
+    assert (bits(exp_o).reshape(-1, 32)[bad] == 0).all() and np.isfinite(exp_o).all()
+
+
 @pytest.fixture(scope="module")
 def no_negotiation(gpu):
     """The collectives refuse to run beside a negotiation, which an earlier test may have started."""

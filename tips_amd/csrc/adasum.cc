@@ -121,7 +121,7 @@ int agree(int size, int n, int64_t total, int dtype, const int64_t* counts, int 
                 r, (long long)q[0], (long long)q[1], (long long)q[2], (unsigned long long)q[3], (long long)q0[0],
                 (long long)q0[1], (long long)q0[2], (unsigned long long)q0[3]);
   }
-  if (!own) TRY(rec.report_refusing("Adasum"));
+  if (!own) TRY(rec.report_refusing("Adasum allreduce"));
   return rec.report_own();
 }
 

@@ -6,9 +6,9 @@
 // A value is quantised twice whatever p is (a ring would requantise at every step).
 // The calls with error feedback (tips_mxfp8_ef_bytes, tips_mxfp8_quantize_ef,
 // tips_mxfp8_fold_ef, tips_allreduce_mxfp8_ef, tips_fused_allreduce_mxfp8_ef_flat) are the same
-// code with a residual: the quantise over the state's sender part, the owner's fold over its owner part.
-#include <math.h>
-
+// code with a residual: the launchers take it as an argument that is null for the plain calls - the
+// quantise over the state's sender part, the owner's fold over its owner part. The factor check, the
+// capturing-stream verdict and the record exchange are side.h's, the segment cover mxfp8.h's.
 #include <algorithm>
 #include <vector>
 
@@ -21,11 +21,6 @@ using namespace tips::rt;
 namespace {
 
 const char kTakes[] = "the MXFP8 calls take";  // need_device's phrase
-
-int check_factor(double factor) {
-  if (!isfinite(factor) || !isfinite((float)factor)) return fail(TIPS_ERR_INVALID_ARG, "factor %g is not a finite float", factor);
-  return 0;
-}
 
 // The list's flat layout: the tensors' element offsets, the flat element count E, and the segments a
 // quantise (cover = true: every flat position up to round_up(E, 256), padding included) or a
@@ -48,12 +43,7 @@ int flat_of(const void* const* ptrs, const int64_t* counts, int n, bool cover, F
       f->segs.push_back(tips::MxSeg{ptrs[i], offs[i] / 4, counts[i], (counts[i] + 31) / 32 * 32});
     }
   std::sort(f->segs.begin(), f->segs.end(), [](const tips::MxSeg& a, const tips::MxSeg& b) { return a.off < b.off; });
-  if (cover) {
-    const int64_t end = tips::mxfp8_scales_offset(f->elems);
-    for (size_t i = 0; i < f->segs.size(); i++)
-      f->segs[i].span = (i + 1 < f->segs.size() ? f->segs[i + 1].off : end) - f->segs[i].off;
-    if (f->segs[0].off > 0) f->segs.insert(f->segs.begin(), tips::MxSeg{nullptr, 0, 0, f->segs[0].off});
-  }
+  if (cover) tips::mxfp8_cover(f->segs, tips::mxfp8_scales_offset(f->elems));
   return 0;
 }
 
@@ -67,11 +57,7 @@ int check_wire(const void* wire, const char* what) {
 int quantize_into(const Flat& f, unsigned char* wire, float* residual, hipStream_t s) {
   const int64_t so = tips::mxfp8_scales_offset(f.elems);
   const int64_t tail_begin = so / tips::kMxBlock, tail_end = tips::mxfp8_wire_bytes(f.elems) - so;
-  if (residual)
-    HIP_TRY(tips::launch_mxfp8_quantize_ef(f.segs.data(), (int)f.segs.size(), wire, wire + so, residual, tail_begin,
-                                           tail_end, s));
-  else
-    HIP_TRY(tips::launch_mxfp8_quantize(f.segs.data(), (int)f.segs.size(), wire, wire + so, tail_begin, tail_end, s));
+  HIP_TRY(tips::launch_mxfp8_quantize(f.segs.data(), (int)f.segs.size(), wire, wire + so, residual, tail_begin, tail_end, s));
   return 0;
 }
 
@@ -131,7 +117,7 @@ int agree(int size, int n, int64_t total, const int64_t* counts, int own, bool w
                 r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)q0[0], (long long)q0[1],
                 (unsigned long long)q0[2]);
   }
-  if (!own) TRY(rec.report_refusing("MXFP8"));
+  if (!own) TRY(rec.report_refusing("MXFP8 allreduce"));
   return rec.report_own();
 }
 
@@ -196,8 +182,7 @@ int run_collective(State& st, const Flat& in, const Flat& out, double factor, fl
         srcs.scales[r] = src.scales;
       }
       const Part dst = blocks_of(w1, mine);
-      if (ef) HIP_TRY(tips::launch_mxfp8_fold_ef(dst.payload, dst.scales, srcs, p, mine.len(), ef + ef_sender_elems(E), s));
-      else HIP_TRY(tips::launch_mxfp8_fold(dst.payload, dst.scales, srcs, p, mine.len(), s));
+      HIP_TRY(tips::launch_mxfp8_fold(dst.payload, dst.scales, srcs, p, mine.len(), ef ? ef + ef_sender_elems(E) : nullptr, s));
     }
     // gather: the reduced chunk `mine` to every peer, every peer's reduced chunk into its place
     TRY(exchange(
@@ -219,12 +204,7 @@ int collective(const char* what, const void* const* ins, const int64_t* counts, 
   std::unique_lock<std::mutex> one;
   int size;
   TRY(side_open(st, st.mxfp8, what, "MXFP8", at_most_max_srcs, /*rccl_only=*/true, &one, &size));
-  // a capturing stream is this rank's refusal, like a pointer it does not accept
-  int own = 0;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-  else if (cs != hipStreamCaptureStatusNone)
-    own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
+  int own = refuse_capture(what, s);
   for (size_t i = 0; i < in.segs.size() && own == 0; i++)
     if (in.segs[i].ptr) own = need_device(in.segs[i].ptr, "an input", kTakes);
   for (size_t i = 0; i < out.segs.size() && own == 0; i++) own = need_device(out.segs[i].ptr, "an output", kTakes);
@@ -263,18 +243,16 @@ int fold_blocks(void* dst_wire, const void* const* src_wires, int nsrc, int64_t 
     srcs.payload[j] = (const unsigned char*)src_wires[j] + block_begin * tips::kMxBlock;
     srcs.scales[j] = (const unsigned char*)src_wires[j] + so + block_begin;
   }
-  unsigned char* d = (unsigned char*)dst_wire;
-  if (!with_ef) {
-    HIP_TRY(tips::launch_mxfp8_fold(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count, s));
-    return 0;
+  if (with_ef) {
+    const int64_t rbytes = 4 * tips::kMxBlock * block_count, wbytes = tips::mxfp8_wire_bytes(flat_elems);
+    TRY(check_residual(residual, rbytes, "residual", nullptr, nullptr));
+    bool hit = overlaps(residual, rbytes, dst_wire, wbytes);
+    for (int j = 0; j < nsrc; j++) hit = hit || overlaps(residual, rbytes, src_wires[j], wbytes);
+    if (hit) return fail(TIPS_ERR_INVALID_ARG, "residual overlaps a wire buffer");
   }
-  const int64_t rbytes = 4 * tips::kMxBlock * block_count, wbytes = tips::mxfp8_wire_bytes(flat_elems);
-  TRY(check_residual(residual, rbytes, "residual", nullptr, nullptr));
-  bool hit = overlaps(residual, rbytes, dst_wire, wbytes);
-  for (int j = 0; j < nsrc; j++) hit = hit || overlaps(residual, rbytes, src_wires[j], wbytes);
-  if (hit) return fail(TIPS_ERR_INVALID_ARG, "residual overlaps a wire buffer");
-  HIP_TRY(tips::launch_mxfp8_fold_ef(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count,
-                                     (float*)residual, s));
+  unsigned char* d = (unsigned char*)dst_wire;
+  HIP_TRY(tips::launch_mxfp8_fold(d + block_begin * tips::kMxBlock, d + so + block_begin, srcs, nsrc, block_count,
+                                  with_ef ? (float*)residual : nullptr, s));
   return 0;
 }
 

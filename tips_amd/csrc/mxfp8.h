@@ -1,9 +1,13 @@
-// mxfp8.h — the MXFP8 wire format's sizes and the launchers of its three kernels and of the two
-// with error feedback (mxfp8.hip). Internal to libtips_hip.so (not part of the C-ABI).
+// mxfp8.h — the MXFP8 wire format's sizes, the segment-cover step of a quantise and the launchers of
+// mxfp8.hip's kernels: quantise and fold (each plain or, given a residual, with error feedback),
+// dequantise and the reduce-scatter's fold-dequantise. Internal to
+// libtips_hip.so (not part of the C-ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <vector>
 
 namespace tips {
 
@@ -28,29 +32,34 @@ struct MxSeg {
 constexpr int kMxSegsPerLaunch = 48;
 constexpr int64_t kMxTileElems = 4096;  // per workgroup: 256 lanes x 4 rounds x 4 elements
 
-// Quantise the segments into the wire buffer (payload, scales: 16-B aligned). `scale_tail`: the
-// scale bytes [scale_tail.first, scale_tail.second) are zeroed by the launch as well (the alignment
-// tail behind the last block; pass {0, 0} for none).
+// Make sorted quantise segments cover every flat position of [0, end): each segment's span reaches
+// the next one's off (the last one's reaches `end`), and where the first does not begin at 0 a
+// padding-only segment is put in front of it. `segs` must not be empty.
+inline void mxfp8_cover(std::vector<MxSeg>& segs, int64_t end) {
+  for (size_t i = 0; i < segs.size(); i++) segs[i].span = (i + 1 < segs.size() ? segs[i + 1].off : end) - segs[i].off;
+  if (segs[0].off > 0) segs.insert(segs.begin(), MxSeg{nullptr, 0, 0, segs[0].off});
+}
+
+// Quantise the segments into the wire buffer (payload, scales: 16-B aligned). The first launch also
+// zeroes the scale bytes scales[tail_begin ... tail_end) (the alignment tail behind the last block;
+// pass 0, 0 for none). `residual` null: the plain quantise. Otherwise the one with error feedback
+// (DESIGN.md §17): the sender residual, one f32 per flat position from position 0 (16-B aligned,
+// round_up(E, 256) floats); c = x + r is quantised and r' = c - dequantise(c) stored, +0 over a
+// poisoned block; positions without a tensor element are not touched.
 hipError_t launch_mxfp8_quantize(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
-                                 int64_t tail_begin, int64_t tail_end, hipStream_t s);
+                                 float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s);
 // dst = quantise(fold of the sources' blocks in order), over `nblocks` blocks: payload pointers at the
 // range's first block (16-B aligned), scale pointers at its first scale byte. dst may be a source.
+// `residual` null: the plain fold. Otherwise the one with error feedback: 32 f32 per block from the
+// range's first block (16-B aligned); c = acc + o is quantised and o' = c - dequantise(c) stored, +0
+// over a poisoned block.
 constexpr int kMxMaxSrcs = 16;
 struct MxSrcs {
   const unsigned char* payload[kMxMaxSrcs];
   const unsigned char* scales[kMxMaxSrcs];
 };
 hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
-                             int64_t nblocks, hipStream_t s);
-// The two with error feedback. Quantise: `residual` is the sender residual, one f32
-// per flat position from position 0 (16-B aligned, round_up(E, 256) floats); c = x + r is quantised
-// and r' = c - dequantise(c) stored, +0 over a poisoned block; positions without a tensor element are
-// not touched. Fold: `residual` is 32 f32 per block from the range's first block (16-B aligned);
-// c = acc + o is quantised and o' = c - dequantise(c) stored, +0 over a poisoned block.
-hipError_t launch_mxfp8_quantize_ef(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
-                                    float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s);
-hipError_t launch_mxfp8_fold_ef(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
-                                int64_t nblocks, float* residual, hipStream_t s);
+                             int64_t nblocks, float* residual, hipStream_t s);
 // Dequantise the segments' elements (segs[i].ptr: the f32 destination) from the wire buffer; factor
 // as an f32 multiply behind the decode when it is not 1.
 hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,

@@ -1,5 +1,6 @@
-// mxfp8.hip — the MXFP8 wire: block-scaled 8-bit quantise, fold-requantise and dequantise,
-// and the quantise and the fold with error feedback (defined where their kernels are).
+// mxfp8.hip — the MXFP8 wire: block-scaled 8-bit quantise, fold-requantise and dequantise.
+// The quantise and the fold each have one device body with two instances: the plain kernel and the
+// one with error feedback (defined where the bodies are). Rules 1-3 below are written once.
 //
 // The operand is the flat f32 layout of a tensor list (fused_layout: tensors at 256-B aligned offsets).
 // A block is 32 consecutive flat elements; it never straddles two tensors; positions that hold no
@@ -37,6 +38,7 @@
 // otherwise, into the same lanes: the same bits. 8 lanes make a block; its maximum takes three
 // cross-lane steps inside a row (DPP). Each lane stores its 4 payload bytes as one dword; the block's
 // first lane stores the scale byte. Fold: 16 payload bytes per lane and source, two lanes per block.
+#include <type_traits>
 #include <vector>
 
 #include "kernels_device.h"
@@ -117,9 +119,39 @@ __device__ __forceinline__ int seg_of_tile(const List& L, int64_t t) {
   return lo;
 }
 
-__global__ __launch_bounds__(kBlock) void mxfp8_quantize_kernel(MxSegList L, unsigned char* __restrict__ payload,
-                                                                unsigned char* __restrict__ scales, int64_t tail_begin,
-                                                                int64_t tail_end) {
+// two payload bytes of a word -> f32 (the hardware's decode), times the block's scale
+template <bool HI>
+__device__ __forceinline__ f32x2 decode2(unsigned w, float scale) {
+#pragma clang fp contract(off)
+  return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI) * scale;
+}
+
+// the new residual of 4 elements c whose payload word is w under the scale byte sb (not poisoned)
+__device__ __forceinline__ f32x4 residual4(f32x4 c, unsigned w, unsigned sb) {
+#pragma clang fp contract(off)
+  const float scale = scale_value(sb);
+  const f32x2 lo = decode2<false>(w, scale), hi = decode2<true>(w, scale);
+  return f32x4{c[0] - lo[0], c[1] - lo[1], c[2] - hi[0], c[3] - hi[1]};
+}
+
+// ---- the quantise and the fold: one body each, plain and with error feedback (§17) ----
+//
+// Error feedback (EF) carries a residual between steps: c = x + r (quantise) or acc + o (fold), one
+// f32 add; c is quantised as the plain form quantises x or acc; y = decode(byte) * 2^(scale byte - 127)
+// through decode2 (the fold's conversion and multiply); the new residual c - y, one f32 subtract,
+// replaces the old one - +0 where the block is poisoned, so that a residual never carries a
+// non-finite value. The residual is read once and written once per step and read again only a step
+// later, behind every other byte the step moves: the quantise, whose residual accesses are whole
+// coalesced lines, makes both sides nontemporal; the fold's are measured (below).
+
+// One tile of the quantise. EF: `residual` is the sender residual, one f32 per flat position (16-B
+// aligned; sg.off is a multiple of 64 and i0 of 4, so a lane's 4 residuals are 16-B aligned whatever
+// the tensor's own address is); positions that hold no tensor element are neither read nor written.
+template <bool EF>
+__device__ __forceinline__ void quantize_tile(const MxSegList& L, unsigned char* __restrict__ payload,
+                                              unsigned char* __restrict__ scales, float* __restrict__ residual,
+                                              int64_t tail_begin, int64_t tail_end) {
+#pragma clang fp contract(off)
   const int tid = threadIdx.x;
   if (blockIdx.x == 0)  // the scale bytes behind the last block, up to the buffer's end
     for (int64_t j = tail_begin + tid; j < tail_end; j += kBlock) scales[j] = 0;
@@ -128,52 +160,117 @@ __global__ __launch_bounds__(kBlock) void mxfp8_quantize_kernel(MxSegList L, uns
   const MxSeg sg = L.seg[si];
   const int64_t base = (t - L.tile0[si]) * kMxTileElems;
   const float* src = (const float*)sg.ptr;
+  float* res = nullptr;
+  if constexpr (EF) res = residual + sg.off;
   const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-  f32x4 x[kMxRounds];
+  f32x4 x[kMxRounds], r[kMxRounds];
+  // The two load phases are kept apart on purpose: the feedback form's nesting compiles the plain
+  // kernel into a different one (fewer registers, another instruction stream), which is a change
+  // to measure on its own.
 #pragma unroll
-  for (int u = 0; u < kMxRounds; u++) {
+  for (int u = 0; u < kMxRounds; u++) {  // all of the lane's loads before the first use
     const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
     x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (vec && i0 + 4 <= sg.count) {
-      x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
-    } else if (i0 < sg.count) {
+    if constexpr (EF) {
+      r[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (i0 + 4 <= sg.count) {
+        r[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(res + i0)));
+        if (vec) {
+          x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
+        } else {
 #pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (i0 + j < sg.count) x[u][j] = src[i0 + j];
+          for (int j = 0; j < 4; j++) x[u][j] = src[i0 + j];
+        }
+      } else if (i0 < sg.count) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < sg.count) x[u][j] = src[i0 + j], r[u][j] = res[i0 + j];
+      }
+    } else {
+      if (vec && i0 + 4 <= sg.count) {
+        x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
+      } else if (i0 < sg.count) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < sg.count) x[u][j] = src[i0 + j];
+      }
     }
   }
 #pragma unroll
   for (int u = 0; u < kMxRounds; u++) {
     const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
-    const unsigned am = max8(abs_max4(x[u]));  // (every lane takes part: lanes past the span hold zeros)
+    f32x4 c = x[u];
+    if constexpr (EF) c = x[u] + r[u];       // (positions without a tensor element: +0 + +0)
+    const unsigned am = max8(abs_max4(c));  // (every lane takes part: lanes past the span hold zeros)
     if (i0 >= sg.span) continue;
     const bool poisoned = am >= kInfBits;
     const unsigned sb = poisoned ? 255u : scale_byte(am);
-    const unsigned w = poisoned ? 0x7f7f7f7fu : encode4(x[u], sb);
+    const unsigned w = poisoned ? 0x7f7f7f7fu : encode4(c, sb);
     *(unsigned*)(payload + sg.off + i0) = w;
     if ((tid & 7) == 0) scales[(sg.off + i0) >> 5] = (unsigned char)sb;
+    if constexpr (EF) {
+      if (i0 >= sg.count) continue;
+      const f32x4 rn = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c, w, sb);
+      if (i0 + 4 <= sg.count) {
+        st16<true>((u32x4*)(res + i0), __builtin_bit_cast(u32x4, rn));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < sg.count) res[i0 + j] = rn[j];
+      }
+    }
   }
 }
 
-// two payload bytes of a word -> f32 (the hardware's decode), times the block's scale
-template <bool HI>
-__device__ __forceinline__ f32x2 decode2(unsigned w, float scale) {
-#pragma clang fp contract(off)
-  return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI) * scale;
+__global__ __launch_bounds__(kBlock) void mxfp8_quantize_kernel(MxSegList L, unsigned char* __restrict__ payload,
+                                                                unsigned char* __restrict__ scales, int64_t tail_begin,
+                                                                int64_t tail_end) {
+  quantize_tile<false>(L, payload, scales, nullptr, tail_begin, tail_end);
 }
 
-__global__ __launch_bounds__(kBlock) void mxfp8_fold_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
-                                                            MxSrcs srcs, int nsrc, int64_t nblocks) {
+__global__ __launch_bounds__(kBlock) void mxfp8_quantize_ef_kernel(MxSegList L, unsigned char* __restrict__ payload,
+                                                                   unsigned char* __restrict__ scales,
+                                                                   float* __restrict__ residual, int64_t tail_begin,
+                                                                   int64_t tail_end) {
+  quantize_tile<true>(L, payload, scales, residual, tail_begin, tail_end);
+}
+
+// The fold of a lane's 16 elements. EF: `residual` is the owner residual of the range, 32 f32 per
+// block from the range's first block (16-B aligned); every position of a block is read and written.
+// A lane's 16 residuals are 64 contiguous bytes, so each of its four 16-B accesses touches a quarter
+// of every 64 B the wave covers and the four together fill the lines: they are plain loads and
+// stores, which lets the caches merge them - measured against the nontemporal forms
+// (profiles/mxfp8_ef/README.md: 34 against 48 us over an eighth of 256 MiB, 16 against 22 us on
+// config 5's list).
+#ifndef TIPS_MXFP8_FOLD_EF_NT_LOAD
+#define TIPS_MXFP8_FOLD_EF_NT_LOAD 0
+#endif
+#ifndef TIPS_MXFP8_FOLD_EF_NT_STORE
+#define TIPS_MXFP8_FOLD_EF_NT_STORE 0
+#endif
+constexpr bool kFoldEfNtLoad = TIPS_MXFP8_FOLD_EF_NT_LOAD, kFoldEfNtStore = TIPS_MXFP8_FOLD_EF_NT_STORE;
+template <bool EF>
+__device__ __forceinline__ void fold_lane(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
+                                          int64_t nblocks, float* residual) {
 #pragma clang fp contract(off)
   const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // 16 elements each: two lanes per block
   const int64_t blk = g >> 1;
   const bool active = blk < nblocks;
   float acc[16];
+  f32x4 o[4];
 #pragma unroll
   for (int j = 0; j < 16; j++) acc[j] = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; q++) o[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  u32x4* og = nullptr;
+  if constexpr (EF) og = (u32x4*)residual + g * 4;
   if (active) {
     u32x4 v = ld16<true>((const u32x4*)srcs.payload[0] + g);
     unsigned sb = srcs.scales[0][blk];
+    if constexpr (EF) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) o[q] = __builtin_bit_cast(f32x4, ld16<kFoldEfNtLoad>(og + q));  // on their way beside source 0
+    }
     for (int k = 0; k < nsrc; k++) {
       const u32x4 cur = v;
       const float scale = scale_value(sb);
@@ -195,158 +292,22 @@ __global__ __launch_bounds__(kBlock) void mxfp8_fold_kernel(unsigned char* dst_p
       }
     }
   }
-  unsigned am = 0;
-#pragma unroll
-  for (int j = 0; j < 16; j++) am = max(am, __builtin_bit_cast(unsigned, acc[j]) & 0x7fffffffu);
-  am = max2(am);
-  if (!active) return;
-  const bool poisoned = am >= kInfBits;
-  const unsigned sb = poisoned ? 255u : scale_byte(am);
-  u32x4 w;
-#pragma unroll
-  for (int q = 0; q < 4; q++)
-    w[q] = poisoned ? 0x7f7f7f7fu : encode4(f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]}, sb);
-  st16<false>((u32x4*)dst_payload + g, w);
-  if ((g & 1) == 0) dst_scales[blk] = (unsigned char)sb;
-}
-
-// ---- error feedback: the two kernels above with a residual carried between steps ----
-//
-// c = x + r (quantise) or acc + o (fold), one f32 add; c is quantised as above; y = decode(byte) *
-// 2^(scale byte - 127) through decode2 (the fold's conversion and multiply); the new residual c - y,
-// one f32 subtract, replaces the old one - +0 where the block is poisoned, so that a residual never
-// carries a non-finite value. The residual is read once and written once per step and read again
-// only a step later, behind every other byte the step moves: the quantise, whose residual accesses
-// are whole coalesced lines, makes both sides nontemporal; the fold's are measured (below).
-
-// the new residual of 4 elements c whose payload word is w under the scale byte sb (not poisoned)
-__device__ __forceinline__ f32x4 residual4(f32x4 c, unsigned w, unsigned sb) {
-#pragma clang fp contract(off)
-  const float scale = scale_value(sb);
-  const f32x2 lo = decode2<false>(w, scale), hi = decode2<true>(w, scale);
-  return f32x4{c[0] - lo[0], c[1] - lo[1], c[2] - hi[0], c[3] - hi[1]};
-}
-
-// mxfp8_quantize_kernel's launch shape. `residual`: the sender residual, one f32 per flat position
-// (16-B aligned; sg.off is a multiple of 64 and i0 of 4, so a lane's 4 residuals are 16-B aligned
-// whatever the tensor's own address is). Positions that hold no tensor element are neither read nor written.
-__global__ __launch_bounds__(kBlock) void mxfp8_quantize_ef_kernel(MxSegList L, unsigned char* __restrict__ payload,
-                                                                   unsigned char* __restrict__ scales,
-                                                                   float* __restrict__ residual, int64_t tail_begin,
-                                                                   int64_t tail_end) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x;
-  if (blockIdx.x == 0)
-    for (int64_t j = tail_begin + tid; j < tail_end; j += kBlock) scales[j] = 0;
-  const int64_t t = blockIdx.x;
-  const int si = seg_of_tile(L, t);
-  const MxSeg sg = L.seg[si];
-  const int64_t base = (t - L.tile0[si]) * kMxTileElems;
-  const float* src = (const float*)sg.ptr;
-  float* res = residual + sg.off;
-  const bool vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-  f32x4 x[kMxRounds], r[kMxRounds];
-#pragma unroll
-  for (int u = 0; u < kMxRounds; u++) {  // all eight loads of the lane before the first use
-    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
-    x[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    r[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + 4 <= sg.count) {
-      r[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(res + i0)));
-      if (vec) {
-        x[u] = __builtin_bit_cast(f32x4, ld16<true>((const u32x4*)(src + i0)));
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) x[u][j] = src[i0 + j];
-      }
-    } else if (i0 < sg.count) {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (i0 + j < sg.count) x[u][j] = src[i0 + j], r[u][j] = res[i0 + j];
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < kMxRounds; u++) {
-    const int64_t i0 = base + ((int64_t)u * kBlock + tid) * 4;
-    const f32x4 c = x[u] + r[u];  // (positions without a tensor element: +0 + +0)
-    const unsigned am = max8(abs_max4(c));
-    if (i0 >= sg.span) continue;
-    const bool poisoned = am >= kInfBits;
-    const unsigned sb = poisoned ? 255u : scale_byte(am);
-    const unsigned w = poisoned ? 0x7f7f7f7fu : encode4(c, sb);
-    *(unsigned*)(payload + sg.off + i0) = w;
-    if ((tid & 7) == 0) scales[(sg.off + i0) >> 5] = (unsigned char)sb;
-    if (i0 >= sg.count) continue;
-    const f32x4 rn = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c, w, sb);
-    if (i0 + 4 <= sg.count) {
-      st16<true>((u32x4*)(res + i0), __builtin_bit_cast(u32x4, rn));
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (i0 + j < sg.count) res[i0 + j] = rn[j];
-    }
-  }
-}
-
-// mxfp8_fold_kernel's launch shape. `residual`: the owner residual of the range, 32 f32 per block from
-// the range's first block (16-B aligned); every position of a block is read and written. A lane's 16
-// residuals are 64 contiguous bytes, so each of its four 16-B accesses touches a quarter of every
-// 64 B the wave covers and the four together fill the lines: they are plain loads and stores, which
-// lets the caches merge them - measured against the nontemporal forms (profiles/mxfp8_ef/README.md:
-// 34 against 48 us over an eighth of 256 MiB, 16 against 22 us on config 5's list).
-#ifndef TIPS_MXFP8_FOLD_EF_NT_LOAD
-#define TIPS_MXFP8_FOLD_EF_NT_LOAD 0
-#endif
-#ifndef TIPS_MXFP8_FOLD_EF_NT_STORE
-#define TIPS_MXFP8_FOLD_EF_NT_STORE 0
-#endif
-constexpr bool kFoldEfNtLoad = TIPS_MXFP8_FOLD_EF_NT_LOAD, kFoldEfNtStore = TIPS_MXFP8_FOLD_EF_NT_STORE;
-__global__ __launch_bounds__(kBlock) void mxfp8_fold_ef_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
-                                                               MxSrcs srcs, int nsrc, int64_t nblocks,
-                                                               float* __restrict__ residual) {
-#pragma clang fp contract(off)
-  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t blk = g >> 1;
-  const bool active = blk < nblocks;
-  float acc[16];
-  f32x4 o[4];
-#pragma unroll
-  for (int j = 0; j < 16; j++) acc[j] = 0.f;
-#pragma unroll
-  for (int q = 0; q < 4; q++) o[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4* const og = (u32x4*)residual + g * 4;
-  if (active) {
-    u32x4 v = ld16<true>((const u32x4*)srcs.payload[0] + g);
-    unsigned sb = srcs.scales[0][blk];
-#pragma unroll
-    for (int q = 0; q < 4; q++) o[q] = __builtin_bit_cast(f32x4, ld16<kFoldEfNtLoad>(og + q));  // on their way beside source 0
-    for (int k = 0; k < nsrc; k++) {
-      const u32x4 cur = v;
-      const float scale = scale_value(sb);
-      if (k + 1 < nsrc) {
-        v = ld16<true>((const u32x4*)srcs.payload[k + 1] + g);
-        sb = srcs.scales[k + 1][blk];
-      }
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const f32x2 lo = decode2<false>(cur[q], scale), hi = decode2<true>(cur[q], scale);
-        if (k == 0) {
-          acc[4 * q] = lo[0], acc[4 * q + 1] = lo[1], acc[4 * q + 2] = hi[0], acc[4 * q + 3] = hi[1];
-        } else {
-          acc[4 * q] = acc[4 * q] + lo[0];
-          acc[4 * q + 1] = acc[4 * q + 1] + lo[1];
-          acc[4 * q + 2] = acc[4 * q + 2] + hi[0];
-          acc[4 * q + 3] = acc[4 * q + 3] + hi[1];
-        }
-      }
-    }
-  }
   f32x4 c[4];
   unsigned am = 0;
+  // The two instances write the block maximum differently on purpose (a max of four abs_max4; one
+  // running max over the 16 values): either expression in the other instance reorders that kernel's
+  // instructions, which is a change to measure on its own.
+  if constexpr (EF) {
 #pragma unroll
-  for (int q = 0; q < 4; q++) {
-    c[q] = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]} + o[q];
-    am = max(am, abs_max4(c[q]));
+    for (int q = 0; q < 4; q++) {
+      c[q] = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]} + o[q];
+      am = max(am, abs_max4(c[q]));
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; j++) am = max(am, __builtin_bit_cast(unsigned, acc[j]) & 0x7fffffffu);
+#pragma unroll
+    for (int q = 0; q < 4; q++) c[q] = f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
   }
   am = max2(am);
   if (!active) return;
@@ -356,11 +317,24 @@ __global__ __launch_bounds__(kBlock) void mxfp8_fold_ef_kernel(unsigned char* ds
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     w[q] = poisoned ? 0x7f7f7f7fu : encode4(c[q], sb);
-    const f32x4 on = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c[q], w[q], sb);
-    st16<kFoldEfNtStore>(og + q, __builtin_bit_cast(u32x4, on));
+    if constexpr (EF) {
+      const f32x4 on = poisoned ? f32x4{0.f, 0.f, 0.f, 0.f} : residual4(c[q], w[q], sb);
+      st16<kFoldEfNtStore>(og + q, __builtin_bit_cast(u32x4, on));
+    }
   }
   st16<false>((u32x4*)dst_payload + g, w);
   if ((g & 1) == 0) dst_scales[blk] = (unsigned char)sb;
+}
+
+__global__ __launch_bounds__(kBlock) void mxfp8_fold_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
+                                                            MxSrcs srcs, int nsrc, int64_t nblocks) {
+  fold_lane<false>(dst_payload, dst_scales, srcs, nsrc, nblocks, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void mxfp8_fold_ef_kernel(unsigned char* dst_payload, unsigned char* dst_scales,
+                                                               MxSrcs srcs, int nsrc, int64_t nblocks,
+                                                               float* __restrict__ residual) {
+  fold_lane<true>(dst_payload, dst_scales, srcs, nsrc, nblocks, residual);
 }
 
 __device__ __forceinline__ float canonical(float y) {
@@ -499,21 +473,25 @@ hipError_t run_fold_segs(const MxFoldList& L, unsigned tiles, float factor, hipS
   return hipGetLastError();
 }
 
-// the launches of a segment list, kMxSegsPerLaunch segments at a time; launch(list, tiles) per part
-template <class F>
-hipError_t for_each_part(const MxSeg* segs, int nseg, bool by_span, F launch) {
-  for (int first = 0; first < nseg; first += kMxSegsPerLaunch) {
-    MxSegList L;
+// The launches of a segment list (L: an MxSegList or an MxFoldList, its other fields set by the
+// caller): each launch's list is filled to its capacity with the next segments; cover(segment) is
+// the elements a launch covers of it; launch(L, tiles) per part. A segment with nothing to cover
+// would be skipped and take no place in a list; every caller passes only segments with something to
+// cover, so a list of n segments takes ceil(n / capacity) launches.
+template <class List, class Seg, class Cover, class F>
+hipError_t for_each_part(List& L, const Seg* segs, int nseg, Cover cover, F launch) {
+  constexpr int kCap = (int)std::extent<decltype(L.seg)>::value;
+  for (int i = 0; i < nseg;) {
     L.nseg = 0;
     int64_t tiles = 0;
-    for (int i = first; i < nseg && i < first + kMxSegsPerLaunch; i++) {
-      const int64_t cover = by_span ? segs[i].span : segs[i].count;
-      if (cover <= 0) continue;
+    for (; i < nseg && L.nseg < kCap; i++) {
+      const int64_t elems = cover(segs[i]);
+      if (elems <= 0) continue;
       L.seg[L.nseg] = segs[i];
       L.tile0[L.nseg++] = tiles;
-      tiles += (cover + kMxTileElems - 1) / kMxTileElems;
+      tiles += (elems + kMxTileElems - 1) / kMxTileElems;
     }
-    if (!L.nseg) continue;
+    if (!L.nseg) break;
     L.tile0[L.nseg] = tiles;
     if (tiles > 0x7fffffff) return hipErrorInvalidValue;
     const hipError_t err = launch(L, (unsigned)tiles);
@@ -525,56 +503,41 @@ hipError_t for_each_part(const MxSeg* segs, int nseg, bool by_span, F launch) {
 }  // namespace
 
 hipError_t launch_mxfp8_quantize(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
-                                 int64_t tail_begin, int64_t tail_end, hipStream_t s) {
+                                 float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s) {
   if (!segs || nseg < 1 || !payload || !scales) return hipErrorInvalidValue;
-  bool first = true;
-  return for_each_part(segs, nseg, true, [&](const MxSegList& L, unsigned tiles) {
-    hipLaunchKernelGGL(mxfp8_quantize_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales,
-                       first ? tail_begin : (int64_t)0, first ? tail_end : (int64_t)0);
-    first = false;
+  MxSegList L;
+  return for_each_part(L, segs, nseg, [](const MxSeg& sg) { return sg.span; }, [&](const MxSegList& part, unsigned tiles) {
+    if (residual)
+      hipLaunchKernelGGL(mxfp8_quantize_ef_kernel, dim3(tiles), dim3(kBlock), 0, s, part, payload, scales, residual,
+                         tail_begin, tail_end);
+    else
+      hipLaunchKernelGGL(mxfp8_quantize_kernel, dim3(tiles), dim3(kBlock), 0, s, part, payload, scales, tail_begin, tail_end);
+    tail_begin = tail_end = 0;  // (the first launch zeroes the tail)
     return hipGetLastError();
   });
 }
 
 hipError_t launch_mxfp8_fold(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
-                             int64_t nblocks, hipStream_t s) {
+                             int64_t nblocks, float* residual, hipStream_t s) {
   if (!dst_payload || !dst_scales || nsrc < 1 || nsrc > kMxMaxSrcs || nblocks < 0) return hipErrorInvalidValue;
   if (nblocks == 0) return hipSuccess;
   const int64_t grid = (2 * nblocks + kBlock - 1) / kBlock;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mxfp8_fold_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
-                     nblocks);
-  return hipGetLastError();
-}
-
-hipError_t launch_mxfp8_quantize_ef(const MxSeg* segs, int nseg, unsigned char* payload, unsigned char* scales,
-                                    float* residual, int64_t tail_begin, int64_t tail_end, hipStream_t s) {
-  if (!segs || nseg < 1 || !payload || !scales || !residual) return hipErrorInvalidValue;
-  bool first = true;
-  return for_each_part(segs, nseg, true, [&](const MxSegList& L, unsigned tiles) {
-    hipLaunchKernelGGL(mxfp8_quantize_ef_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales, residual,
-                       first ? tail_begin : (int64_t)0, first ? tail_end : (int64_t)0);
-    first = false;
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_mxfp8_fold_ef(unsigned char* dst_payload, unsigned char* dst_scales, const MxSrcs& srcs, int nsrc,
-                                int64_t nblocks, float* residual, hipStream_t s) {
-  if (!dst_payload || !dst_scales || nsrc < 1 || nsrc > kMxMaxSrcs || nblocks < 0 || !residual) return hipErrorInvalidValue;
-  if (nblocks == 0) return hipSuccess;
-  const int64_t grid = (2 * nblocks + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mxfp8_fold_ef_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
-                     nblocks, residual);
+  if (residual)
+    hipLaunchKernelGGL(mxfp8_fold_ef_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
+                       nblocks, residual);
+  else
+    hipLaunchKernelGGL(mxfp8_fold_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, dst_payload, dst_scales, srcs, nsrc,
+                       nblocks);
   return hipGetLastError();
 }
 
 hipError_t launch_mxfp8_dequantize(const MxSeg* segs, int nseg, const unsigned char* payload, const unsigned char* scales,
                                    float factor, hipStream_t s) {
   if (!segs || nseg < 1 || !payload || !scales) return hipErrorInvalidValue;
-  return for_each_part(segs, nseg, false, [&](const MxSegList& L, unsigned tiles) {
-    hipLaunchKernelGGL(mxfp8_dequantize_kernel, dim3(tiles), dim3(kBlock), 0, s, L, payload, scales, factor,
+  MxSegList L;
+  return for_each_part(L, segs, nseg, [](const MxSeg& sg) { return sg.count; }, [&](const MxSegList& part, unsigned tiles) {
+    hipLaunchKernelGGL(mxfp8_dequantize_kernel, dim3(tiles), dim3(kBlock), 0, s, part, payload, scales, factor,
                        factor != 1.0f ? 1 : 0);
     return hipGetLastError();
   });
@@ -596,31 +559,16 @@ hipError_t launch_mxfp8_fold_segs(const MxFoldSeg* segs, int nseg, const MxSrcs&
   L.srcs = wires;
   L.nsrc = nsrc;
   L.own_pos = own_pos;
-  int i = 0;
-  while (i < nseg) {
-    L.nseg = 0;
-    int64_t tiles = 0;
-    for (; i < nseg && L.nseg < kMxFoldSegsPerLaunch; i++) {
-      if (segs[i].count <= 0) continue;
-      L.seg[L.nseg] = segs[i];
-      L.tile0[L.nseg++] = tiles;
-      tiles += (segs[i].count + kMxTileElems - 1) / kMxTileElems;
-    }
-    if (!L.nseg) break;
-    L.tile0[L.nseg] = tiles;
-    if (tiles > 0x7fffffff) return hipErrorInvalidValue;
-    hipError_t err;
+  return for_each_part(L, segs, nseg, [](const MxFoldSeg& sg) { return sg.count; }, [&](const MxFoldList& part, unsigned tiles) {
     switch (nsrc) {
 #define TIPS_MX_FOLD_SEGS_CASE(K) \
-  case K: err = run_fold_segs<K>(L, (unsigned)tiles, factor, s); break;
+  case K: return run_fold_segs<K>(part, tiles, factor, s);
       TIPS_MX_FOLD_SEGS_CASE(2) TIPS_MX_FOLD_SEGS_CASE(3) TIPS_MX_FOLD_SEGS_CASE(4) TIPS_MX_FOLD_SEGS_CASE(5)
       TIPS_MX_FOLD_SEGS_CASE(6) TIPS_MX_FOLD_SEGS_CASE(7) TIPS_MX_FOLD_SEGS_CASE(8)
 #undef TIPS_MX_FOLD_SEGS_CASE
-      default: err = run_fold_segs<kMxMaxSrcs>(L, (unsigned)tiles, factor, s);
+      default: return run_fold_segs<kMxMaxSrcs>(part, tiles, factor, s);
     }
-    if (err != hipSuccess) return err;
-  }
-  return hipSuccess;
+  });
 }
 
 }  // namespace tips

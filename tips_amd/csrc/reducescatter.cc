@@ -8,7 +8,8 @@
 // tips_reducescatter_mxfp8, tips_grouped_reducescatter_mxfp8) is the same exchange with the peer
 // regions quantised once (mxfp8.hip's quantise) and the owner's fold reading wire bytes beside its
 // own f32 slices (mxfp8.hip's fold-dequantise).
-#include <math.h>
+// Both kinds of collective go through one entry path, enter(): an entry keeps its own checks on its
+// scalar arguments, its words of the record, its mismatch text and its schedule.
 #include <string.h>
 
 #include <algorithm>
@@ -185,77 +186,84 @@ int run_collective(State& st, const Call& c, hipStream_t s) {
   return st.rscatter.close(s);
 }
 
-int collective(const char* what, const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
-               int n, int dtype, int op, double pre, double post, hipStream_t s) {
+// What a collective entry brings beside its Call. Every rank's record is eight words: the tensor
+// count (-1 where the list cannot be read), the element count, the shape hash, `words` and, last,
+// the rank's verdict. A call of one kind paired with a call of the other on another rank is a
+// mismatch on both sides: `kind` is folded into the shape hash.
+struct Entry {
+  const char *what, *noun;  // "tips_reducescatter", "reduce-scatter"
+  uint64_t kind;            // 0: the plain calls, their record as it always was; 0xF8: the MXFP8 calls
+  int64_t words[4];         // the record's words 3 ... 6
+  int (*mismatch)(int r, const int64_t* q, const int64_t* q0);  // fail(TIPS_ERR_MISMATCH, ...) on rank r's record and rank 0's
+};
+
+// The path every collective entry takes. `own`: the verdict of the entry's own checks on its scalar
+// arguments; run(st) is its schedule, called under st.mu and st.rscatter.mu.
+template <class Run>
+int enter(const Entry& e, const Call& c, int own, hipStream_t s, Run run) {
   // What needs no device comes first; once the call is open it is part of this rank's verdict, so
   // that a rank which refuses its arguments does not leave the others waiting in the exchange.
+  const int n = c.n;
   int64_t total = 0;
-  int own = check_op(dtype, op, pre, post);
-  if (own == 0) own = check_shapes(rows, row_elems, n, tips::dtype_size(dtype), &total);
-  if (own == 0 && n > 0 && (!ins || !outs)) own = fail(TIPS_ERR_INVALID_ARG, "null pointer list");
+  if (own == 0) own = check_shapes(c.rows, c.row_elems, n, c.es, &total);
+  if (own == 0 && n > 0 && (!c.ins || !c.outs)) own = fail(TIPS_ERR_INVALID_ARG, "null pointer list");
   const bool usable = own == 0;  // the list can be read
   const std::string early = own ? last_error() : std::string();
   State& st = S();
   std::unique_lock<std::mutex> one;
   int size;
-  if (const int rc = side_open(st, st.rscatter, what, "reduce-scatter", at_most_max_srcs, /*rccl_only=*/true, &one, &size))
+  if (const int rc = side_open(st, st.rscatter, e.what, e.noun, at_most_max_srcs, /*rccl_only=*/true, &one, &size))
     return own ? fail(own, "%s", early.c_str()) : rc;
-  Call c{ins, outs, rows, row_elems, n, dtype, tips::dtype_size(dtype), scale_of(op, pre, post)};
-  if (own) {
-    (void)fail(own, "%s", early.c_str());
-  } else {
-    // a capturing stream is this rank's refusal, like a pointer it does not accept
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-    else if (cs != hipStreamCaptureStatusNone)
-      own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
-    if (own == 0) {
-      int rank;
-      {
-        std::lock_guard<std::mutex> lk(st.mu);
-        rank = st.rank;
-      }
-      own = check_pointers(c, size, rank);
+  if (own) (void)fail(own, "%s", early.c_str());
+  else own = refuse_capture(e.what, s);
+  if (own == 0) {
+    int rank;
+    {
+      std::lock_guard<std::mutex> lk(st.mu);
+      rank = st.rank;
     }
+    own = check_pointers(c, size, rank);
   }
   uint64_t h = kFnvBasis;
   if (usable) {
     std::vector<int64_t> shape((size_t)2 * n);
-    for (int i = 0; i < n; i++) shape[2 * i] = rows[i], shape[2 * i + 1] = row_elems[i];
+    for (int i = 0; i < n; i++) shape[2 * i] = c.rows[i], shape[2 * i + 1] = c.row_elems[i];
     h = hash_counts(shape.data(), 2 * n);
   }
-  const int64_t mine[8] = {usable ? n : -1, total, (int64_t)h, dtype, op, (int64_t)bits_of(pre), (int64_t)bits_of(post), own};
+  if (e.kind) h = (h ^ e.kind) * kFnvPrime;
+  const int64_t mine[8] = {usable ? n : -1, total, (int64_t)h, e.words[0], e.words[1], e.words[2], e.words[3], own};
   SideRecords rec;
   TRY(side_exchange(size, mine, 8, &rec));
   // reported in this order: a mismatch, another rank's refusal, this rank's own
-  if (const int r = rec.first_differing(0, 7); r >= 0) {
-    const int64_t *q = rec.of(r), *q0 = rec.of(0);
-    return fail(TIPS_ERR_MISMATCH,
-                "Mismatched reduce-scatter: rank %d has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
-                "factor bits %llx / %llx; rank 0 has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
-                "factor bits %llx / %llx",
-                r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)q[3], (long long)q[4],
-                (unsigned long long)q[5], (unsigned long long)q[6], (long long)q0[0], (long long)q0[1],
-                (unsigned long long)q0[2], (long long)q0[3], (long long)q0[4], (unsigned long long)q0[5],
-                (unsigned long long)q0[6]);
-  }
-  if (!own)
-    if (const int r = rec.first_refusing(); r >= 0)
-      return fail(TIPS_ERR_MISMATCH, "reduce-scatter: rank %d refused its arguments (status %lld)", r, (long long)rec.of(r)[7]);
+  if (const int r = rec.first_differing(0, 7); r >= 0) return e.mismatch(r, rec.of(r), rec.of(0));
+  if (!own) TRY(rec.report_refusing(e.noun));
   TRY(rec.report_own());
   if (total == 0) return 0;
   std::lock_guard<std::mutex> lk(st.mu);
   if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
   TRY(set_device(st));
-  return run_collective(st, c, s);
+  return run(st);
+}
+
+int mismatch(int r, const int64_t* q, const int64_t* q0) {
+  return fail(TIPS_ERR_MISMATCH,
+              "Mismatched reduce-scatter: rank %d has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
+              "factor bits %llx / %llx; rank 0 has %lld tensors, %lld elements, shape hash %llx, dtype %lld, op %lld, "
+              "factor bits %llx / %llx",
+              r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (long long)q[3], (long long)q[4],
+              (unsigned long long)q[5], (unsigned long long)q[6], (long long)q0[0], (long long)q0[1],
+              (unsigned long long)q0[2], (long long)q0[3], (long long)q0[4], (unsigned long long)q0[5],
+              (unsigned long long)q0[6]);
+}
+
+int collective(const char* what, const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
+               int n, int dtype, int op, double pre, double post, hipStream_t s) {
+  const Call c{ins, outs, rows, row_elems, n, dtype, tips::dtype_size(dtype), scale_of(op, pre, post)};
+  const Entry e{what, "reduce-scatter", 0, {dtype, op, (int64_t)bits_of(pre), (int64_t)bits_of(post)}, mismatch};
+  return enter(e, c, check_op(dtype, op, pre, post), s, [&](State& st) { return run_collective(st, c, s); });
 }
 
 // ---- the MXFP8 reduce-scatter ----
-
-int check_factor(double factor) {
-  if (!isfinite(factor) || !isfinite((float)factor)) return fail(TIPS_ERR_INVALID_ARG, "factor %g is not a finite float", factor);
-  return 0;
-}
 
 uint32_t float_bits_of(double x) {
   const float f = (float)x;
@@ -264,24 +272,31 @@ uint32_t float_bits_of(double x) {
   return u;
 }
 
-// Region q of a list as the MXFP8 wire sees it: the slices' element counts, their flat element
-// offsets under tips_fused_layout(counts, n, FLOAT32) and the flat element count E_q
+// A count list as the MXFP8 wire sees it: the tensors' element counts, their flat element offsets
+// under tips_fused_layout(counts, n, FLOAT32) and the flat element count E (all 0 for an empty list)
 struct MxRegion {
   std::vector<int64_t> counts, offs;
   int64_t elems = 0;
 };
 
-MxRegion mx_region(const int64_t* rows, const int64_t* row_elems, int n, int p, int q) {
+MxRegion mx_region_of(std::vector<int64_t> counts) {
   MxRegion r;
-  r.counts.resize((size_t)n);
-  r.offs.assign((size_t)n, 0);
+  r.counts = std::move(counts);
+  r.offs.assign(r.counts.size(), 0);
   int64_t total = 0;
-  for (int i = 0; i < n; i++) total += r.counts[i] = tips::rs_rows(rows[i], p, q, nullptr) * row_elems[i];
+  for (const int64_t c : r.counts) total += c;
   if (total > 0) {
-    r.elems = fused_layout(r.counts.data(), n, TIPS_FLOAT32, r.offs.data()) / 4;
-    for (int i = 0; i < n; i++) r.offs[i] /= 4;
+    r.elems = fused_layout(r.counts.data(), (int)r.counts.size(), TIPS_FLOAT32, r.offs.data()) / 4;
+    for (int64_t& o : r.offs) o /= 4;
   }
   return r;
+}
+
+// region q of a list: its slices' counts
+MxRegion mx_region(const int64_t* rows, const int64_t* row_elems, int n, int p, int q) {
+  std::vector<int64_t> counts((size_t)n);
+  for (int i = 0; i < n; i++) counts[i] = tips::rs_rows(rows[i], p, q, nullptr) * row_elems[i];
+  return mx_region_of(std::move(counts));
 }
 
 // the order the kernels want: ascending flat offset (the layout puts a tensor of at least the fusion
@@ -335,11 +350,9 @@ int run_mx_collective(State& st, const Call& c, double factor, hipStream_t s) {
           segs.push_back(tips::MxSeg{from, base[q] + reg[q].offs[i], elems, 0});
         }
       }
-      for (size_t i = 0; i < segs.size(); i++)  // a segment covers the padding up to the next one
-        segs[i].span = (i + 1 < segs.size() ? segs[i + 1].off : send_elems) - segs[i].off;
-      if (segs[0].off > 0) segs.insert(segs.begin(), tips::MxSeg{nullptr, 0, 0, segs[0].off});
-      HIP_TRY(tips::launch_mxfp8_quantize(segs.data(), (int)segs.size(), send, send + send_elems, send_elems / tips::kMxBlock,
-                                          send_bytes - send_elems, s));
+      tips::mxfp8_cover(segs, send_elems);
+      HIP_TRY(tips::launch_mxfp8_quantize(segs.data(), (int)segs.size(), send, send + send_elems, nullptr,
+                                          send_elems / tips::kMxBlock, send_bytes - send_elems, s));
     }
     const int64_t in_blocks = tips::mxfp8_blocks(mine.elems);
     TRY(rccl_enter(st, s));
@@ -374,68 +387,20 @@ int run_mx_collective(State& st, const Call& c, double factor, hipStream_t s) {
   return st.rscatter.close(s);
 }
 
+int mx_mismatch(int r, const int64_t* q, const int64_t* q0) {
+  return fail(TIPS_ERR_MISMATCH,
+              "Mismatched MXFP8 reduce-scatter: rank %d has %lld tensors, %lld elements, call and shape hash %llx, factor bits "
+              "%llx; rank 0 has %lld tensors, %lld elements, call and shape hash %llx, factor bits %llx",
+              r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (unsigned long long)q[5], (long long)q0[0],
+              (long long)q0[1], (unsigned long long)q0[2], (unsigned long long)q0[5]);
+}
+
 int mx_collective(const char* what, const void* const* ins, void* const* outs, const int64_t* rows, const int64_t* row_elems,
                   int n, double factor, hipStream_t s) {
-  // as collective() above: what needs no device first, then part of this rank's verdict
-  int64_t total = 0;
-  int own = check_factor(factor);
-  if (own == 0) own = check_shapes(rows, row_elems, n, 4, &total);
-  if (own == 0 && n > 0 && (!ins || !outs)) own = fail(TIPS_ERR_INVALID_ARG, "null pointer list");
-  const bool usable = own == 0;
-  const std::string early = own ? last_error() : std::string();
-  State& st = S();
-  std::unique_lock<std::mutex> one;
-  int size;
-  if (const int rc = side_open(st, st.rscatter, what, "MXFP8 reduce-scatter", at_most_max_srcs, /*rccl_only=*/true, &one, &size))
-    return own ? fail(own, "%s", early.c_str()) : rc;
-  Call c{ins, outs, rows, row_elems, n, TIPS_FLOAT32, 4, tips::Scale()};
-  if (own) {
-    (void)fail(own, "%s", early.c_str());
-  } else {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-    else if (cs != hipStreamCaptureStatusNone)
-      own = fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
-    if (own == 0) {
-      int rank;
-      {
-        std::lock_guard<std::mutex> lk(st.mu);
-        rank = st.rank;
-      }
-      own = check_pointers(c, size, rank);
-    }
-  }
-  // The record has the plain reduce-scatter's eight words, so that a call paired with
-  // tips_reducescatter / tips_grouped_reducescatter on another rank is a mismatch there and here: the
-  // call kind is folded into the shape hash, the factor's float bits stand where the prescale's do.
-  uint64_t h = kFnvBasis;
-  if (usable) {
-    std::vector<int64_t> shape((size_t)2 * n);
-    for (int i = 0; i < n; i++) shape[2 * i] = rows[i], shape[2 * i + 1] = row_elems[i];
-    h = hash_counts(shape.data(), 2 * n);
-  }
-  h = (h ^ 0xF8ull) * kFnvPrime;
-  const int64_t mine[8] = {usable ? n : -1, total, (int64_t)h, TIPS_FLOAT32, TIPS_OP_SUM, (int64_t)float_bits_of(factor), 0, own};
-  SideRecords rec;
-  TRY(side_exchange(size, mine, 8, &rec));
-  if (const int r = rec.first_differing(0, 7); r >= 0) {
-    const int64_t *q = rec.of(r), *q0 = rec.of(0);
-    return fail(TIPS_ERR_MISMATCH,
-                "Mismatched MXFP8 reduce-scatter: rank %d has %lld tensors, %lld elements, call and shape hash %llx, factor bits "
-                "%llx; rank 0 has %lld tensors, %lld elements, call and shape hash %llx, factor bits %llx",
-                r, (long long)q[0], (long long)q[1], (unsigned long long)q[2], (unsigned long long)q[5], (long long)q0[0],
-                (long long)q0[1], (unsigned long long)q0[2], (unsigned long long)q0[5]);
-  }
-  if (!own)
-    if (const int r = rec.first_refusing(); r >= 0)
-      return fail(TIPS_ERR_MISMATCH, "MXFP8 reduce-scatter: rank %d refused its arguments (status %lld)", r,
-                  (long long)rec.of(r)[7]);
-  TRY(rec.report_own());
-  if (total == 0) return 0;
-  std::lock_guard<std::mutex> lk(st.mu);
-  if (!st.initialized) return fail(TIPS_ERR_NOT_INITIALIZED, "tips_init has not been called");
-  TRY(set_device(st));
-  return run_mx_collective(st, c, factor, s);
+  const Call c{ins, outs, rows, row_elems, n, TIPS_FLOAT32, 4, tips::Scale()};
+  // the plain record's words with the factor's float bits where the prescale's stand
+  const Entry e{what, "MXFP8 reduce-scatter", 0xF8, {TIPS_FLOAT32, TIPS_OP_SUM, (int64_t)float_bits_of(factor), 0}, mx_mismatch};
+  return enter(e, c, check_factor(factor), s, [&](State& st) { return run_mx_collective(st, c, factor, s); });
 }
 
 }  // namespace
@@ -537,11 +502,7 @@ int tips_reducescatter_mxfp8_fold(void* const* outs, const void* const* own, con
       if (!wires[j]) return fail(TIPS_ERR_INVALID_ARG, "null pointer (wire %d)", j);
       if (reinterpret_cast<uintptr_t>(wires[j]) & 15) return fail(TIPS_ERR_INVALID_ARG, "wire %d is not 16-B aligned", j);
     }
-  MxRegion r;
-  r.counts.assign(counts, counts + n);
-  r.offs.assign((size_t)n, 0);
-  r.elems = fused_layout(counts, n, TIPS_FLOAT32, r.offs.data()) / 4;
-  for (int i = 0; i < n; i++) r.offs[i] /= 4;
+  const MxRegion r = mx_region_of(std::vector<int64_t>(counts, counts + n));
   std::vector<tips::MxFoldSeg> segs;
   for (int i : by_offset(r)) segs.push_back(tips::MxFoldSeg{own[i], outs[i], r.offs[i], counts[i]});
   // (like tips_reducescatter_fold, the kernel's own entry does not probe its pointers)

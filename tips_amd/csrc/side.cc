@@ -1,6 +1,8 @@
 // side.cc — the protocol the collectives beside the negotiation share (side.h).
 #include "side.h"
 
+#include <math.h>
+
 #include <algorithm>
 
 namespace tips {
@@ -29,6 +31,21 @@ uint64_t hash_counts(const int64_t* counts, int n) {
   for (int i = 0; i < n; i++)
     for (int k = 0; k < 8; k++) h = (h ^ (((uint64_t)counts[i] >> (8 * k)) & 0xff)) * kFnvPrime;
   return h;
+}
+
+int check_factor(double factor) {
+  if (!isfinite(factor) || !isfinite((float)factor)) return fail(TIPS_ERR_INVALID_ARG, "factor %g is not a finite float", factor);
+  return 0;
+}
+
+int refuse_capture(const char* what, hipStream_t s) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  if (cs == hipStreamCaptureStatusNone) return 0;
+  return fail(TIPS_ERR_UNSUPPORTED, "%s is never captured into a graph (its stream is capturing)", what);
 }
 
 int side_open(State& st, SideChain& chain, const char* what, const char* noun, RankRule ranks, bool rccl_only,
@@ -72,11 +89,10 @@ int SideRecords::first_refusing() const {
   return -1;
 }
 
-int SideRecords::report_refusing(const char* noun) const {
+int SideRecords::report_refusing(const char* call) const {
   const int r = first_refusing();
   if (r < 0) return 0;
-  return fail(TIPS_ERR_MISMATCH, "%s allreduce: rank %d refused its arguments (status %lld)", noun, r,
-              (long long)of(r)[words - 1]);
+  return fail(TIPS_ERR_MISMATCH, "%s: rank %d refused its arguments (status %lld)", call, r, (long long)of(r)[words - 1]);
 }
 
 }  // namespace rt

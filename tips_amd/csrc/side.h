@@ -1,5 +1,6 @@
 // side.h — what the collectives that run beside the negotiation share (sparse.cc, adasum.cc,
-// mxfp8.cc): the argument checks, how a call opens, and the record exchange in which
+// mxfp8.cc, reducescatter.cc): the argument checks (pointers, counts, the f32 factor,
+// the capturing stream), how a call opens, and the record exchange in which
 // every rank learns whether all ranks bring the same call and accept their own pointers before any
 // of them enters a device exchange. The scratch they chain their calls on is rt.h's SideChain.
 #pragma once
@@ -14,6 +15,11 @@ int need_device(const void* p, const char* what, const char* feature);
 // the counts of a list of `noun`s ("segment", "tensor"): none negative, the total (at most 2^56) in *total
 int check_counts(const int64_t* counts, int n, const char* noun, int64_t* total);
 uint64_t hash_counts(const int64_t* counts, int n);  // FNV-1a over the counts' bytes
+// a factor the f32 kernels multiply by: finite as a double and as a float, or TIPS_ERR_INVALID_ARG
+int check_factor(double factor);
+// 0, or TIPS_ERR_UNSUPPORTED "<what> is never captured into a graph" where the stream is capturing:
+// this rank's refusal, like a pointer it does not accept (a query that fails counts as not capturing)
+int refuse_capture(const char* what, hipStream_t s);
 
 // How a call opens. Refuses a call on, or beside, a running negotiation (`noun`: "sparse", "Adasum",
 // "MXFP8"); takes the chain's mutex into *one; then, under st.mu: the lifecycle, the device, *size,
@@ -34,7 +40,8 @@ struct SideRecords {
   int first_differing(int lo, int hi) const;  // the first rank whose words [lo, hi) are not rank 0's, or -1
   int first_refusing() const;                 // the first rank whose verdict is not 0, or -1
   int report_own() const { return own ? fail(own, "%s", own_msg.c_str()) : 0; }
-  int report_refusing(const char* noun) const;  // TIPS_ERR_MISMATCH "rank r refused its arguments", or 0
+  // TIPS_ERR_MISMATCH "<call>: rank r refused its arguments" (`call`: "sparse allreduce", "reduce-scatter", ...), or 0
+  int report_refusing(const char* call) const;
 };
 // mine[words - 1] is the verdict; st.mu must not be held (tips_allgather_i64; one rank: a copy)
 int side_exchange(int size, const int64_t* mine, int words, SideRecords* rec);

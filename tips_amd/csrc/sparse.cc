@@ -100,7 +100,7 @@ int tips_sparse_allreduce(const void* values, const int64_t* indices, int64_t n,
                 "row_elems %lld, dtype %lld",
                 r, (long long)q[1], (long long)q[2], (long long)q[3], (long long)q0[1], (long long)q0[2], (long long)q0[3]);
   }
-  TRY(rec.report_refusing("sparse"));
+  TRY(rec.report_refusing("sparse allreduce"));
   if (!active) return 0;
   const int64_t es = tips::dtype_size(dtype);
   std::vector<int64_t> counts(size), vcounts(size);
