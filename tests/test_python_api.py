@@ -570,3 +570,229 @@ def test_overlap_trial_with_any_warmup(monkeypatch, warm):
         assert s < 20
     assert oc.chosen is True and oc.report["chosen"] == "during"
     assert s == oc.warm + 4
+
+
+# --- which C entries a gradient list reaches ---------------------------------------------------
+# Every entry point goes through the one funnel tips_amd._lib.call; the spy below logs
+# (entry name, list length where the entry takes one, the factors it was given) and returns 0.
+_AG = ("tips_allgather_i64",), ("tips_allgatherv",)  # one allgather_op: the first dimensions, then the rows
+_REG = ("tips_host_register",)                        # a new host output set is page-locked
+_AR = ("tips_allreduce",)
+_AR_S = "tips_allreduce_scaled"                       # (prescale, postscale)
+_FLAT = "tips_fused_allreduce_flat"                   # (n)
+_FLAT_S = "tips_fused_allreduce_flat_scaled"          # (n, prescale, postscale)
+_CAST = "tips_fused_allreduce_cast"                   # (n)
+_SCALE = "tips_scale"                                 # (factor)
+_HOST = "tips_fused_allreduce_host_flat"              # (n)
+_MX = "tips_fused_allreduce_mxfp8_flat"               # (n, factor)
+_MX1 = "tips_allreduce_mxfp8"                         # (factor)
+_EFB = ("tips_mxfp8_ef_bytes",)                       # the size of a list's error-feedback state
+_MXEF = "tips_fused_allreduce_mxfp8_ef_flat"          # (n, factor)
+
+# entry -> (position of the list length among its arguments or None, positions of its factors)
+_ROUTE_ARGS = {_FLAT: (2, ()), _FLAT_S: (2, (5, 6)), _CAST: (3, ()), _HOST: (2, ()), _MX: (2, (4,)), _MXEF: (2, (4,)),
+               _AR_S: (None, (4, 5)), _MX1: (None, (3,)), _SCALE: (None, (4,))}
+
+_INT_DEV = "op=Average is not defined for integer gradients (dtype torch.int32)"
+_INT_HOST = "op=Average is not defined for integer gradients (dtype int32)"
+_EF_LIST = ("allreduce_grads(fused=False) does not combine with MXFP8 error feedback: the residual state belongs to "
+            "the fused list")
+_EF_BODY = "fused=False does not combine with MXFP8 error feedback"
+_NO_MAX = ("op=Max is not supported for gradient lists: the fused reductions carry SUM only (reduce single tensors "
+           "with allreduce(tensor, op=Max))")
+_NO_MIN = ("op=Min is not supported for gradient lists: the fused reductions carry SUM only (reduce single tensors "
+           "with allreduce(tensor, op=Min))")
+
+
+def _route_list(which):
+    """The lists of the route test. Device members: f32 [5], f32 [4099] as a stride-2 view, f16 [3],
+    i32 [4]; host members: numpy f32 [7], CPU torch f64 [2, 3]; a host sparse COO tensor, a host
+    IndexedSlices and None."""
+    import torch
+    import tips_amd
+
+    def dev(*shape, dtype=torch.float32):
+        return torch.zeros(*shape, dtype=dtype, device="cuda")
+
+    def host():
+        return [np.zeros(7, np.float32), torch.zeros(2, 3, dtype=torch.float64)]
+
+    def sparse():
+        return [torch.sparse_coo_tensor([[0, 2]], [1.0, 2.0], (4,)),
+                tips_amd.IndexedSlices(np.zeros((3, 2), np.float32), np.array([4, 0, 4], np.int64), dense_shape=(5, 2)),
+                None]
+    if which == "fast":       # one dtype of contiguous device tensors: the fast list
+        return [dev(5), dev(2, 3), dev(4)]
+    if which == "dev2":       # two device dtypes: not a fast list, but a split a plan remembers
+        return [dev(5), dev(6), dev(3, dtype=torch.float16)]
+    if which == "mixed":      # everything
+        return [dev(5), dev(8198)[::2], dev(3, dtype=torch.float16), dev(4, dtype=torch.int32)] + host() + sparse()
+    if which == "mixed_float":  # everything that takes a scale (an integer under Average raises)
+        return [dev(5), dev(8198)[::2], dev(3, dtype=torch.float16)] + host() + sparse()
+    if which == "host":
+        return host()
+    if which == "host_sparse":
+        return host() + sparse()
+    if which == "host_int":
+        return [np.zeros(4, np.int32), np.zeros(7, np.float32)]
+    raise KeyError(which)
+
+
+def _route_rows():
+    """(id, list, compression, op, scaling, fused, gradient_predivide_factor, expected): `expected`
+    is the log of each call of the list (calls after the first repeat it with the same tensor
+    objects) and how many of the calls ran a remembered plan - or the message of the ValueError.
+    At size() == 2 Average is (prescale 1, postscale 0.5), with gradient_predivide_factor 2 it is
+    (0.5, 1); the MXFP8 wire and the cast path get the product."""
+    A = "Average"
+    sparse2 = [*_AG, *_AG, *_AG, *_AG]  # the COO tensor's indices and values, the IndexedSlices' values and indices
+    host2 = [_REG, (_HOST, 1), _REG, (_HOST, 1)]  # numpy f32 and torch f64: one host group each, new sets
+    rows = [
+        # the fast list: three contiguous float32 device tensors
+        ("fast-none", "fast", "none", None, False, True, 1, ([[(_FLAT, 3)], [(_FLAT, 3)]], 0)),
+        ("fast-none-average-unscaled", "fast", "none", A, False, True, 1, ([[(_FLAT, 3)]], 0)),
+        ("fast-none-sum-scaling", "fast", "none", None, True, True, 2, ([[(_FLAT, 3)]], 0)),
+        ("fast-none-average", "fast", "none", A, True, True, 1, ([[(_FLAT_S, 3, 1.0, 0.5)], [(_FLAT_S, 3, 1.0, 0.5)]], 0)),
+        ("fast-none-average-predivide", "fast", "none", A, True, True, 2, ([[(_FLAT_S, 3, 0.5, 1.0)]], 0)),
+        ("fast-none-unfused", "fast", "none", None, False, False, 1, ([[_AR, _AR, _AR]], 0)),
+        ("fast-none-average-unfused", "fast", "none", A, True, False, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)]], 0)),
+        ("fast-fp16", "fast", "fp16", None, False, True, 1, ([[(_CAST, 3)], [(_CAST, 3)]], 0)),
+        ("fast-fp16-average", "fast", "fp16", A, True, True, 1, ([[(_CAST, 3), (_SCALE, 0.5)]], 0)),
+        ("fast-fp16-average-predivide", "fast", "fp16", A, True, True, 2, ([[(_CAST, 3), (_SCALE, 0.5)]], 0)),
+        ("fast-fp16-unfused", "fast", "fp16", None, False, False, 1, ([[_AR, _AR, _AR]], 0)),
+        ("fast-fp16-average-unfused", "fast", "fp16", A, True, False, 2,
+         ([[(_AR_S, 0.5, 1.0), (_AR_S, 0.5, 1.0), (_AR_S, 0.5, 1.0)]], 0)),
+        ("fast-fp8", "fast", "fp8", None, False, True, 1, ([[(_MX, 3, 1.0)]], 0)),
+        ("fast-fp8-average-predivide", "fast", "fp8", A, True, True, 2, ([[(_MX, 3, 0.5)]], 0)),
+        ("fast-fp8-average-unfused", "fast", "fp8", A, True, False, 1, ([[(_MX1, 0.5), (_MX1, 0.5), (_MX1, 0.5)]], 0)),
+        ("fast-ef", "fast", "ef", None, False, True, 1, ([[_EFB, (_MXEF, 3, 1.0)], [_EFB, (_MXEF, 3, 1.0)]], 0)),
+        ("fast-ef-average", "fast", "ef", A, True, True, 1, ([[_EFB, (_MXEF, 3, 0.5)]], 0)),
+        # two device dtypes: the second call runs the remembered plan (unscaled only)
+        ("dev2-none", "dev2", "none", None, False, True, 1, ([[(_FLAT, 2), (_FLAT, 1)], [(_FLAT, 2), (_FLAT, 1)]], 1)),
+        ("dev2-none-average", "dev2", "none", A, True, True, 1,
+         ([[(_FLAT_S, 2, 1.0, 0.5), (_FLAT_S, 1, 1.0, 0.5)], [(_FLAT_S, 2, 1.0, 0.5), (_FLAT_S, 1, 1.0, 0.5)]], 0)),
+        # the mixed list: sparse members inside the loop, then device groups (f32 x 2, f16, i32), then
+        # cast groups, then host groups
+        ("mixed-none", "mixed", "none", None, False, True, 1,
+         ([sparse2 + [(_FLAT, 2), (_FLAT, 1), (_FLAT, 1)] + host2], 0)),
+        ("mixed-none-average-unscaled", "mixed", "none", A, False, True, 2,
+         ([sparse2 + [(_FLAT, 2), (_FLAT, 1), (_FLAT, 1)] + host2], 0)),
+        ("mixed-none-unfused", "mixed", "none", None, False, False, 1, ([[_AR, _AR, _AR, _AR, _AR, _AR] + sparse2], 0)),
+        ("mixed-fp16", "mixed", "fp16", None, False, True, 1,
+         ([sparse2 + [(_FLAT, 1), (_FLAT, 1), (_CAST, 2)] + host2], 0)),
+        ("mixed-fp8", "mixed", "fp8", None, False, True, 1,
+         ([[(_MX, 2, 1.0)] + sparse2 + [(_FLAT, 1), (_FLAT, 1)] + host2], 0)),
+        ("mixed-ef", "mixed", "ef", None, False, True, 1,
+         ([[_EFB, (_MXEF, 2, 1.0)] + sparse2 + [(_FLAT, 1), (_FLAT, 1)] + host2], 0)),
+        ("mixed-none-average-integer", "mixed", "none", A, True, True, 1, _INT_DEV),
+        # under a scale: host members one scaled allreduce each (inside the loop, before the sparse
+        # ones that follow them in the list), device groups after the loop
+        ("mixed_float-none-average", "mixed_float", "none", A, True, True, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2 + [(_FLAT_S, 2, 1.0, 0.5), (_FLAT_S, 1, 1.0, 0.5)]], 0)),
+        ("mixed_float-none-average-predivide", "mixed_float", "none", A, True, True, 2,
+         ([[(_AR_S, 0.5, 1.0), (_AR_S, 0.5, 1.0)] + sparse2 + [(_FLAT_S, 2, 0.5, 1.0), (_FLAT_S, 1, 0.5, 1.0)]], 0)),
+        ("mixed_float-fp16-average", "mixed_float", "fp16", A, True, True, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2 + [(_CAST, 2), (_SCALE, 0.5)]], 0)),
+        ("mixed_float-fp8-average", "mixed_float", "fp8", A, True, True, 1,
+         ([[(_MX, 2, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2 + [(_FLAT_S, 1, 1.0, 0.5)]], 0)),
+        ("mixed_float-ef-average", "mixed_float", "ef", A, True, True, 1,
+         ([[_EFB, (_MXEF, 2, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2 + [(_FLAT_S, 1, 1.0, 0.5)]], 0)),
+        ("mixed_float-none-average-unfused", "mixed_float", "none", A, True, False, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2], 0)),
+        # host members only: no device, so these rows run everywhere
+        ("host-none", "host", "none", None, False, True, 1, ([host2, [(_HOST, 1), (_HOST, 1)]], 1)),
+        ("host-none-average-unscaled", "host", "none", A, False, True, 1, ([host2], 0)),
+        ("host-none-average", "host", "none", A, True, True, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)], [(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)]], 0)),
+        ("host-none-unfused", "host", "none", None, False, False, 1, ([[_AR, _AR]], 0)),
+        ("host-fp16", "host", "fp16", None, False, True, 1, ([host2, [(_HOST, 1), (_HOST, 1)]], 0)),
+        ("host-fp16-average", "host", "fp16", A, True, True, 1, ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)]], 0)),
+        ("host-fp8", "host", "fp8", None, False, True, 1, ([host2], 0)),
+        ("host-fp8-average-predivide", "host", "fp8", A, True, True, 2, ([[(_AR_S, 0.5, 1.0), (_AR_S, 0.5, 1.0)]], 0)),
+        ("host-ef", "host", "ef", None, False, True, 1, ([host2], 0)),
+        ("host_sparse-none", "host_sparse", "none", None, False, True, 1, ([sparse2 + host2], 0)),
+        ("host_sparse-none-average", "host_sparse", "none", A, True, True, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2], 0)),
+        ("host_sparse-fp16-average-unfused", "host_sparse", "fp16", A, True, False, 1,
+         ([[(_AR_S, 1.0, 0.5), (_AR_S, 1.0, 0.5)] + sparse2], 0)),
+        # the refusals: nothing reaches the library
+        ("host_int-none-average-integer", "host_int", "none", A, True, True, 1, _INT_HOST),
+        ("host-ef-unfused", "host", "ef", None, False, False, 1, _EF_LIST),
+        ("host-ef-unfused-body", "host", "ef", None, False, False, 1, _EF_BODY),
+        ("host-none-max", "host", "none", "Max", False, True, 1, _NO_MAX),
+        ("host-none-min-body", "host", "none", "Min", True, True, 1, _NO_MIN),
+    ]
+    out = []
+    for row in rows:
+        marks = [] if row[1].startswith("host") else [pytest.mark.gpu]
+        out.append(pytest.param(*row[1:], id=row[0], marks=marks))
+    return out
+
+
+@pytest.mark.parametrize("which,compression,op,scaling,fused,predivide,expected", _route_rows())
+def test_gradient_list_routes(monkeypatch, request, which, compression, op, scaling, fused, predivide, expected):
+    """Which C entries allreduce_grads reaches for a list, in which order, with how many tensors and
+    which factors: a route that fell to the unfused path would give the same bits, only slower. Two
+    ranks are faked (size() == 2, init a no-op) and tips_amd._lib.call is a spy that logs and returns
+    0, so nothing is launched and the outputs are not looked at; tips_fused_layout (pure host, not
+    through the funnel) runs for real, and so does _remember_plan. Rows whose id ends in -body call
+    _reduce_grads, allreduce_grads' N > 1 body, directly: its checks hold there too."""
+    import tips_amd
+    ops = tips_amd._ops
+    log = []
+
+    def spy(name, *args):
+        n_at, factors_at = _ROUTE_ARGS.get(name, (None, ()))
+        log.append((name,) + (() if n_at is None else (int(args[n_at]),)) + tuple(float(args[k]) for k in factors_at))
+        return 0
+
+    plan_runs = []
+    real_run = tips_amd._GradPlan.run
+
+    def counted_run(self, grads):
+        plan_runs.append(len(grads))
+        return real_run(self, grads)
+
+    monkeypatch.setattr(tips_amd._lib, "call", spy)
+    monkeypatch.setattr(tips_amd, "size", lambda: 2)
+    monkeypatch.setattr(tips_amd.basics, "size", lambda: 2)  # (the allgather of a sparse member asks there)
+    monkeypatch.setattr(tips_amd, "init", lambda: None)
+    monkeypatch.setattr(tips_amd.basics, "init", lambda: None)
+    monkeypatch.setattr(tips_amd._GradPlan, "run", counted_run)
+    monkeypatch.setattr(ops, "_check", False)
+    # the spy page-locks nothing, so the host sets made here have nothing to unregister when they go
+    # (the real call would leave a HIP error behind for whoever asks the runtime next)
+    monkeypatch.setattr(ops, "_unregister", lambda ptr: None)
+    for mod, cache, fresh in ((ops, "_FLAT_OUTPUTS", {}), (ops, "_FAST_FLAT", {}), (ops, "_HOST_FLAT", {}),
+                              (tips_amd, "_PLANS", [])):
+        monkeypatch.setattr(mod, cache, fresh)  # no set or plan of another test, and none of this one left behind
+    was = ops.op_scaling()
+    tips_amd.set_op_scaling(scaling)
+    try:
+        grads = _route_list(which)
+        comp = {"none": tips_amd.Compression.none, "fp16": tips_amd.Compression.fp16, "fp8": tips_amd.Compression.fp8,
+                "ef": tips_amd.Compression.fp8.error_feedback()}[compression]
+        body = request.node.callspec.id.endswith("-body")
+
+        def reduce():
+            if body:
+                return tips_amd._reduce_grads(grads, compression=comp, op=op, fused=fused,
+                                              gradient_predivide_factor=predivide)
+            return tips_amd.allreduce_grads(grads, compression=comp, op=op, fused=fused,
+                                            gradient_predivide_factor=predivide)
+        if isinstance(expected, str):
+            with pytest.raises(ValueError) as e:
+                reduce()
+            assert str(e.value) == expected and log == []
+            return
+        logs, planned = expected
+        for want in logs:
+            del log[:]
+            out = reduce()
+            assert len(out) == len(grads) and [o is None for o in out] == [g is None for g in grads]
+            del out  # (released: the next call of the list gets the same output sets)
+            assert log == want
+        assert len(plan_runs) == planned
+    finally:
+        tips_amd.set_op_scaling(was)

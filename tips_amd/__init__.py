@@ -229,7 +229,7 @@ def allreduce(tensor,
         new_values = (values / size()) if op == Average else values
         return IndexedSlices(new_values, indices, dense_shape=tensor.dense_shape)
     if _tensors.is_torch(tensor) and tensor.is_sparse:
-        import torch
+        torch = _ops._torch()
         idx = tensor._indices().t().contiguous()  # (nnz, ndim): rows concatenate along dim 0
         vals = tensor._values().contiguous()
         g_idx = allgather_op(idx).t()
@@ -253,17 +253,24 @@ def allreduce(tensor,
     return compression.decompress(summed_tensor_compressed, ctx)
 
 
+def _no_factors(op, prescale_factor, postscale_factor, why):
+    if float(prescale_factor) != 1.0 or float(postscale_factor) != 1.0:
+        raise ValueError("op=%s takes no prescale_factor / postscale_factor: %s" % (op, why))
+
+
+def _no_name(op, name):
+    if name is not None:
+        raise ValueError("op=%s takes no name: named requests go through the negotiation, which carries SUM only" % op)
+
+
 def _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor, name):
     """allreduce(op=Max | Min): the argument checks (before anything is initialised), then compress,
     reduce, decompress."""
-    if float(prescale_factor) != 1.0 or float(postscale_factor) != 1.0:
-        raise ValueError("op=%s takes no prescale_factor / postscale_factor: scaling does not combine with a "
-                         "maximum or minimum" % op)
+    _no_factors(op, prescale_factor, postscale_factor, "scaling does not combine with a maximum or minimum")
     if isinstance(tensor, IndexedSlices) or (_tensors.is_torch(tensor) and tensor.is_sparse):
         raise ValueError("op=%s is not defined for sparse inputs (their allgather branch sums repeated indices): "
                          "densify first" % op)
-    if name is not None:
-        raise ValueError("op=%s takes no name: named requests go through the negotiation, which carries SUM only" % op)
+    _no_name(op, name)
     tensor_compressed, ctx = compression.compress(tensor)
     return compression.decompress(allreduce_reduce_op(tensor_compressed, op), ctx)
 
@@ -271,10 +278,8 @@ def _allreduce_minmax(tensor, compression, op, prescale_factor, postscale_factor
 def _allreduce_adasum(tensor, compression, prescale_factor, postscale_factor, name):
     """allreduce(op=Adasum): the argument checks (before anything is initialised), then compress,
     reduce, decompress."""
-    if float(prescale_factor) != 1.0 or float(postscale_factor) != 1.0:
-        raise ValueError("op=Adasum takes no prescale_factor / postscale_factor: there is no scaled Adasum")
-    if name is not None:
-        raise ValueError("op=Adasum takes no name: named requests go through the negotiation, which carries SUM only")
+    _no_factors(Adasum, prescale_factor, postscale_factor, "there is no scaled Adasum")
+    _no_name(Adasum, name)
     if isinstance(tensor, IndexedSlices):
         raise ValueError("op=Adasum is not defined for sparse inputs: densify first")
     _ops.check_adasum_tensor(tensor)
@@ -350,7 +355,7 @@ def _sparse_parts(slices, scaled):
                          "gradients go through the allgather branch, allreduce(IndexedSlices)")
     if values.device != indices.device:
         raise ValueError("values and indices must be on one device")
-    import torch
+    torch = _ops._torch()
     if indices.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
         raise ValueError("indices must be integers (got %s)" % indices.dtype)
     if len(shape) < 1 or indices.dim() != 1 or values.dim() < 1 or values.shape[0] != indices.shape[0] or \
@@ -381,7 +386,7 @@ def sparse_allreduce(slices, op=None, prescale_factor=1.0, postscale_factor=1.0,
     pre, post = float(prescale_factor), float(postscale_factor)
     values, indices, shape = _sparse_parts(slices, op == Average or pre != 1.0 or post != 1.0)
     code = _tensors.dtype_code(values)
-    import torch
+    torch = _ops._torch()
     init()
     if op == Average:
         post = post / size()
@@ -445,7 +450,7 @@ def _to_dense(g):
         if g.dense_shape is None:
             raise ValueError("sparse_as_dense needs the IndexedSlices' dense_shape")
         if _tensors.is_torch(g.values):
-            import torch
+            torch = _ops._torch()
             dense = torch.zeros(tuple(int(d) for d in g.dense_shape), dtype=g.values.dtype, device=g.values.device)
             idx = g.indices if _tensors.is_torch(g.indices) else torch.as_tensor(g.indices)
             return dense.index_add_(0, idx.to(dense.device, torch.int64), g.values)
@@ -517,7 +522,7 @@ def allreduce_grads(grads, compression=Compression.none, op=None, fused=True, sp
         grads = [_to_dense(g) if g is not None else g for g in grads]
     if size() <= 1:
         return list(grads)
-    return _reduce_grads(grads, compression, op, fused, gradient_predivide_factor)
+    return _reduce_checked(grads, compression, op, fused, gradient_predivide_factor)
 
 
 def _reduce_grads_sparse(grads, compression, op, fused, gradient_predivide_factor):
@@ -535,7 +540,12 @@ def _reduce_grads_sparse(grads, compression, op, fused, gradient_predivide_facto
         else:
             rest.append(_to_dense(g) if g is not None else g)
     if size() > 1 and any(g is not None for g in rest):
-        rest = _reduce_grads(rest, compression, op, fused, gradient_predivide_factor)
+        rest = _reduce_checked(rest, compression, op, fused, gradient_predivide_factor)
+    return _merged(out, rest)
+
+
+def _merged(out, rest):
+    """`out` with every entry of `rest` that is not None in its place: a list reduced in two parts."""
     for i, g in enumerate(rest):
         if g is not None:
             out[i] = g
@@ -549,6 +559,42 @@ def _average_scale(op, gradient_predivide_factor=1.0):
     return _op_scale(op, 1.0 / f, f) if op == Average else _op_scale(op)
 
 
+def _route(g, compression, scale, fused):
+    """The way one gradient of a list takes through _reduce_grads - the route table. `scale` is
+    (prescale, postscale), or None for the plain sum (set_op_scaling off, or nothing to scale).
+
+      gradient                                      scale is None       under a scale
+      sparse (IndexedSlices, torch sparse)          "own"               "own"
+      dense, fused=False                            "own"               "scaled"
+      device float32 under Compression.fp16         "cast"              "cast"
+      device, Compression.none                      "dev"               "dev"
+      device, another compressor or dtype           "dev"               "scaled"
+      host (numpy, CPU torch)                       "host"              "scaled"
+
+    "own": allreduce(g, compression=compression, op=op), inside the loop - a sparse gradient's
+    allgather branch, which divides for op=Average whatever the switch says. "dev": compressed, then
+    with its (dtype, device) group through tips_fused_allreduce_flat, under a scale
+    tips_fused_allreduce_flat_scaled with the factors inside each bucket's sums. "cast": with its
+    device's group through the fused cast path, fp16 on the wire; under a scale followed by one
+    tips_scale per flat output buffer (unfused). "host": compressed, then with its dtype group through
+    fused_allreduce_host_flat. "scaled": compressed, one allreduce_scaled, inside the loop - the host
+    path and the compressed device groups have no scaled entry. Under a scale an integer gradient that
+    is not sparse raises ValueError, and no plan is looked up or remembered."""
+    if scale is None and not fused:
+        return "own"
+    kind = _kind(g)
+    if kind is None:
+        return "own"
+    if scale is not None and _ops._is_integer(g):
+        raise ValueError("op=Average is not defined for integer gradients (dtype %s)" % g.dtype)
+    if fused and kind == "dev":
+        if compression is FP16Compressor and g.dtype == _ops._torch().float32:
+            return "cast"
+        if scale is None or compression is Compression.none:
+            return "dev"
+    return "host" if scale is None else "scaled"
+
+
 def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, gradient_predivide_factor=1.0):
     """What allreduce_grads runs at N > 1 (bench.py times it on one rank, where allreduce_grads
     itself is the identity). With fused=True:
@@ -559,27 +605,31 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
         dtype: fused_allreduce_host_flat - packed into page-locked pieces by host threads,
         pipelined H2D -> allreduce -> D2H straight into one page-locked flat host buffer, the
         outputs views of it (reused as the device flat outputs are);
-      - the rest (sparse) one by one, through the reference's allgather branch."""
-    _no_minmax_grads(op)
+      - the rest (sparse) one by one, through the reference's allgather branch.
+    Under set_op_scaling(True) with something to scale (op=Average at N > 1) every gradient is
+    postscale * SUM(prescale * g); _route says which entry carries the factors."""
+    if op in (Max, Min):
+        _no_minmax_grads(op)
+    if not fused and _is_ef(compression):
+        raise ValueError("fused=False does not combine with MXFP8 error feedback")
+    return _reduce_checked(grads, compression, op, fused, gradient_predivide_factor)
+
+
+def _reduce_checked(grads, compression, op, fused, gradient_predivide_factor):
+    """_reduce_grads behind its argument checks (allreduce_grads has made them already)."""
     if compression is MXFP8Compressor or _is_ef(compression):
         return _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor, compression if _is_ef(compression) else None)
     none = compression is Compression.none
-    global _DATA_PTR
-    if _DATA_PTR is None:
-        import torch
-        _DATA_PTR = torch.Tensor.data_ptr
     scale = _average_scale(op, gradient_predivide_factor)
-    if scale is not None:
-        return _reduce_grads_scaled(grads, compression, scale, fused)
-    if fused and grads and compression is FP16Compressor:  # (one list of dense f32 device tensors)
+    if fused and grads and scale is None and compression is FP16Compressor:  # (one list of dense f32 device tensors)
         res = _ops._dev_list_cast(grads)
         if res is not None:
             return res
     if fused and none and grads:
-        res = _ops._dev_list_flat(grads)  # (one dtype of dense device tensors: the common case)
+        res = _ops._dev_list_flat(grads, scale)  # (one dtype of dense device tensors: the common case)
         if res is not None:
             return res
-        plan = _find_plan(grads)
+        plan = _find_plan(grads) if scale is None else None
         if plan is not None:  # the same tensor objects as a recent call: no per-tensor inspection
             res = plan.run(grads)
             if res is not None:
@@ -587,43 +637,40 @@ def _reduce_grads(grads, compression=Compression.none, op=None, fused=True, grad
             _PLANS.remove(plan)
     out = list(grads)
     dev, host, cast = {}, {}, {}
-    simple = fused and none  # only dense, contiguous device tensors: the split can be remembered
-    fp16 = fused and compression is FP16Compressor
+    simple = fused and none and scale is None  # only dense, contiguous device tensors: the split can be remembered
     for i, g in enumerate(grads):
         if g is None:
             continue
-        if not fused:
-            out[i] = allreduce(g, compression=compression, op=op)
-            continue
-        kind = _kind(g)
-        if kind is None:
+        route = _route(g, compression, scale, fused)
+        if route == "own":
             out[i] = allreduce(g, compression=compression, op=op)
             simple = False
-            continue
-        if fp16 and kind == "dev" and g.dtype == _torch().float32:
+        elif route == "cast":
             # Compression.fp16 fused into the buckets: cast while packed, fp16 on the wire, cast back
             # while unpacked (tips_fused_allreduce_cast) - no per-tensor cast launches
             cast.setdefault(g.device, []).append((i, g if g.is_contiguous() else g.contiguous()))
-            continue
-        c, ctx = (g, None) if none else compression.compress(g)
-        if kind == "dev":
-            if not c.is_contiguous():
-                c = c.contiguous()
-                simple = False
-            dev.setdefault((c.dtype, c.device), []).append((i, c, ctx))
         else:
-            c = _tensors.contiguous(c)
-            host.setdefault(str(c.dtype), []).append((i, c, ctx))
+            c, ctx = (g, None) if none else compression.compress(g)
+            if route == "scaled":
+                s = allreduce_scaled(c, scale[0], scale[1])
+                out[i] = s if none else compression.decompress(s, ctx)
+            elif route == "dev":
+                if not c.is_contiguous():
+                    c = c.contiguous()
+                    simple = False
+                dev.setdefault((c.dtype, c.device), []).append((i, c, ctx))
+            else:
+                c = _tensors.contiguous(c)
+                host.setdefault(str(c.dtype), []).append((i, c, ctx))
     plan_groups = []
     for members in dev.values():
         ts = [c for _, c, _ in members]
-        fo = _ops._flat_outputs(ts, _tensors.dtype_code(ts[0]))
-        sums = _ops._flat_run(fo, ts, list(map(_DATA_PTR, ts)))
+        sums = _ops._flat_call(ts, _tensors.dtype_code(ts[0]), list(map(_ops._torch().Tensor.data_ptr, ts)), scale)
         for (i, _, ctx), s in zip(members, sums):
             out[i] = s if none else compression.decompress(s, ctx)
         plan_groups.append(([i for i, _, _ in members], None, None))
     for members in cast.values():
-        for (i, _), s in zip(members, _ops.fused_allreduce_cast([c for _, c in members], "float16")):
+        for (i, _), s in zip(members, _ops.fused_allreduce_cast([c for _, c in members], "float16", scale)):
             out[i] = s
     for members in host.values():
         ts = [c for _, c, _ in members]
@@ -651,8 +698,6 @@ def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor, ef=None):
     the factor prescale * postscale of set_op_scaling multiplied in double; the rest of the list as
     under Compression.none. `ef`: an MXFP8ErrorFeedback - per device one fused_allreduce_mxfp8_ef over
     its state of (device, counts, size())."""
-    if ef is not None and not fused:
-        raise ValueError("fused=False does not combine with MXFP8 error feedback")
     scale = _average_scale(op, gradient_predivide_factor)
     factor = 1.0 if scale is None else scale[0] * scale[1]
     out, rest, groups = list(grads), [], {}
@@ -675,59 +720,10 @@ def _reduce_grads_mxfp8(grads, op, fused, gradient_predivide_factor, ef=None):
         for (i, _), s in zip(members, sums):
             out[i] = s
     if any(g is not None for g in rest):
-        for i, g in enumerate(_reduce_grads(rest, Compression.none, op, fused, gradient_predivide_factor)):
-            if g is not None:
-                out[i] = g
-    return out
+        rest = _reduce_checked(rest, Compression.none, op, fused, gradient_predivide_factor)
+    return _merged(out, rest)
 
 
-def _reduce_grads_scaled(grads, compression, scale, fused=True):
-    """_reduce_grads under set_op_scaling(True) with something to scale (op=Average at N > 1):
-    postscale * SUM(prescale * g) per gradient. Dense device gradients, per dtype, through
-    tips_fused_allreduce_flat_scaled - the factors inside each bucket's sums; float32 device
-    gradients under Compression.fp16 through the fused cast path, then one tips_scale per flat
-    output buffer (unfused); every other dense gradient (host tensors, other compressors) one
-    allreduce_scaled each; sparse ones through the allgather branch, which divides for Average."""
-    none = compression is Compression.none
-    if fused and none and grads:
-        res = _ops._dev_list_flat(grads, scale)  # (one dtype of dense device tensors: the common case)
-        if res is not None:
-            return res
-    out = list(grads)
-    dev, cast = {}, {}
-    for i, g in enumerate(grads):
-        if g is None:
-            continue
-        kind = _kind(g)
-        if kind is None:
-            out[i] = allreduce(g, compression=compression, op=Average)
-            continue
-        if _ops._is_integer(g):
-            raise ValueError("op=Average is not defined for integer gradients (dtype %s)" % g.dtype)
-        if fused and kind == "dev" and compression is FP16Compressor and g.dtype == _torch().float32:
-            cast.setdefault(g.device, []).append((i, g if g.is_contiguous() else g.contiguous()))
-        elif fused and kind == "dev" and none:
-            dev.setdefault((g.dtype, g.device), []).append((i, g if g.is_contiguous() else g.contiguous()))
-        else:
-            c, ctx = compression.compress(g)
-            out[i] = compression.decompress(allreduce_scaled(c, scale[0], scale[1]), ctx)
-    for members in dev.values():
-        ts = [c for _, c in members]
-        fo = _ops._flat_outputs(ts, _tensors.dtype_code(ts[0]))
-        for (i, _), s in zip(members, _ops._flat_run(fo, ts, list(map(_DATA_PTR, ts)), scale)):
-            out[i] = s
-    for members in cast.values():
-        for (i, _), s in zip(members, _ops.fused_allreduce_cast([c for _, c in members], "float16", scale)):
-            out[i] = s
-    return out
-
-
-_DATA_PTR = None  # torch.Tensor.data_ptr, bound on first use
-
-
-def _torch():
-    import torch
-    return torch
 _PLANS = []       # recent _GradPlans, most recent first
 
 

@@ -14,6 +14,7 @@ from . import _fast  # (built in-tree by `make`: tips_amd/_fast*.so; no Python f
 from . import _lib
 from . import basics
 from . import tensors
+from .tensors import _torch  # torch, imported on first use (tips_amd/__init__.py uses this accessor too)
 
 
 def _normalize_name(name):
@@ -179,7 +180,7 @@ class _HostOutPool(object):
         if sys.getrefcount(a) > 3:  # (the entry, the local a, getrefcount's argument)
             return False
         if e[1] is not None:  # torch: no other tensor on the storage
-            import torch
+            torch = _torch()
             return torch._C._storage_Use_Count(a.untyped_storage()._cdata) == e[1]
         return True
 
@@ -200,7 +201,7 @@ class _HostOutPool(object):
                 if _lib.lib().tips_host_register(tensors.data_ptr(out), nbytes) == 0:
                     use0 = None
                     if is_t:
-                        import torch
+                        torch = _torch()
                         use0 = torch._C._storage_Use_Count(out.untyped_storage()._cdata)
                     lst.append((out, use0))
                     self.bytes += nbytes
@@ -233,7 +234,7 @@ def allgather_op(tensor, name=None):
     counts = [int(f) * row for f in firsts]
     out_shape = (sum(int(f) for f in firsts),) + shape[1:]
     if tensors.is_torch(src):
-        import torch
+        torch = _torch()
         out = torch.empty(out_shape, dtype=src.dtype, device=src.device)
     else:
         import numpy as np
@@ -350,62 +351,86 @@ def fused_allreduce_cast(tensor_list, wire="float16", scale=None):
     res = _dev_list_cast(tensor_list, _WIRE_CODES[wire], scale)  # (dense, contiguous, one device: C++ reads the list)
     if res is not None:
         return res
-    fo = _flat_outputs(tensor_list, code)
-    flat, views = fo.take()
-    pi, _keep1 = _lib.ptr_array([t.data_ptr() for t in tensor_list])
-    _lib.call("tips_fused_allreduce_cast", pi, _out_ptrs(fo, flat), fo.cp[0], len(tensor_list), code, _WIRE_CODES[wire],
-              tensors.stream_of(tensor_list[0]))
+    fo, pi, flat, views = _take_outputs(tensor_list, code)
+    _lib.call("tips_fused_allreduce_cast", pi[0], _out_ptrs(fo, flat), fo.cp[0], len(tensor_list), code,
+              _WIRE_CODES[wire], tensors.stream_of(tensor_list[0]))
     if scale is not None:
         scale_(flat, float(scale[0]) * float(scale[1]))
     return views
 
 
-class _FlatOutputs(object):
-    """Output sets of fused_allreduce_flat for one list signature (dtype, device, shapes): the
-    layout's byte offsets (tips_fused_layout: a function of the counts alone) and a few sets of
-    {one flat buffer, one view of it per tensor}. A set is handed out again once every tensor of
-    it has been released by the caller: no Python reference to any of its views, and no other
-    tensor sharing its storage (derived views included). Allocating the buffer and 1000 views per
-    call costs milliseconds of host time - more than the device work of the whole allreduce."""
+def _cache_put(cache, key, value, limit=16):
+    """cache[key] = value in a small dict kept in insertion order: at `limit` entries the oldest goes
+    first. Returns value."""
+    if len(cache) >= limit:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
+class _OutputSets(object):
+    """What the output sets of one list signature share, device (_FlatOutputs) or host
+    (_HostFlatOutputs): the layout's byte offsets (tips_fused_layout: a function of the counts
+    alone), the count array and dtype code of the library call, the pointer array of the previous
+    call, and up to MAX_SETS sets of {one flat buffer, one view of it per tensor}, sets[i][0] the
+    flat buffer. A subclass says how a set is allocated (_new_set) and how its release by the caller
+    is measured (_released)."""
 
     MAX_SETS = 4
 
-    def __init__(self, shapes, numels, code, dtype, device):
-        import torch
-        self.numels = numels
+    def __init__(self, numels, code):
         import ctypes
-        cp, _keep = _lib.i64_array(numels)
+        self.numels, self.code = numels, code
+        self.cp = _lib.i64_array(numels)
         offs = (ctypes.c_int64 * len(numels))()
-        self.total = _lib.check("tips_fused_layout", _lib.lib().tips_fused_layout(cp, len(numels), code, offs))
-        self.es = torch.empty((), dtype=dtype).element_size()
-        self.offs = [int(o) // self.es for o in offs]
-        self.shapes, self.dtype, self.device = shapes, dtype, device
+        self.total = _lib.check("tips_fused_layout", _lib.lib().tips_fused_layout(self.cp[0], len(numels), code, offs))
+        self.offs = [int(o) for o in offs]
         self.sets = []
+        self.last = (None, None)  # (pointer list, its ptr_array) of the previous call
         self.lock = threading.Lock()  # (the free check and the hand-out together, as _HostOutPool)
 
-    def _free(self, s):
+    def take(self):
+        """(flat buffer, a new list of its views) for this call: a released set, or a new one (kept
+        while there are fewer than MAX_SETS). The list is made here, before the library call releases
+        the GIL, so another thread's take() already sees the set's views referenced and does not hand
+        it out twice."""
+        with self.lock:  # another thread's take() cannot see a set free between the check and the copy
+            for s in self.sets:
+                if self._released(s):
+                    return s[0], list(s[1])
+            return self._new_set(len(self.sets) < self.MAX_SETS)
+
+
+class _FlatOutputs(_OutputSets):
+    """Output sets of fused_allreduce_flat for one list signature (dtype, device, shapes). A set is
+    handed out again once every tensor of it has been released by the caller: no Python reference
+    to any of its views, and no other tensor sharing its storage (derived views included).
+    Allocating the buffer and 1000 views per call costs milliseconds of host time - more than the
+    device work of the whole allreduce."""
+
+    def __init__(self, shapes, numels, code, dtype, device):
+        _OutputSets.__init__(self, numels, code)
+        self.es = _itemsize(dtype, True)
+        self.shapes, self.dtype, self.device = shapes, dtype, device
+        # bound here, once per signature: the release check and the stream lookup run on every call
+        self.use_count = _torch()._C._storage_Use_Count
+        self.cur_stream = _torch().cuda.current_stream
+
+    def _released(self, s):
         flat, views, use0, rc0 = s
-        import torch
-        if torch._C._storage_Use_Count(flat.untyped_storage()._cdata) != use0:
+        if self.use_count(flat.untyped_storage()._cdata) != use0:
             return False
         return _fast.max_refcount(views) <= rc0
 
-    def take(self):
-        """(flat buffer, a new list of its views) for this call: a released set, or a new one. The
-        list is made here, before the library call releases the GIL, so another thread's take()
-        already sees the set's views referenced and does not hand it out twice."""
-        import torch
-        with self.lock:  # another thread's take() cannot see a set free between the check and the copy
-            for s in self.sets:
-                if self._free(s):
-                    return s[0], list(s[1])
-            flat = torch.empty(max(1, self.total // self.es), dtype=self.dtype, device=self.device)
-            views = [flat[o:o + n].view(shp) for o, n, shp in zip(self.offs, self.numels, self.shapes)]
-            if len(self.sets) < self.MAX_SETS:
-                use0 = torch._C._storage_Use_Count(flat.untyped_storage()._cdata)
-                rc0 = _fast.max_refcount(views)
-                self.sets.append((flat, views, use0, rc0))
-            return flat, list(views)
+    def _new_set(self, keep):
+        es = self.es
+        flat = _torch().empty(max(1, self.total // es), dtype=self.dtype, device=self.device)
+        views = [flat[o // es:o // es + n].view(shp) for o, n, shp in zip(self.offs, self.numels, self.shapes)]
+        if keep:
+            use0 = self.use_count(flat.untyped_storage()._cdata)
+            rc0 = _fast.max_refcount(views)
+            self.sets.append((flat, views, use0, rc0))
+        return flat, list(views)
 
 
 _FLAT_OUTPUTS = {}  # (dtype, device, shapes, layout settings) -> _FlatOutputs (small LRU)
@@ -439,18 +464,34 @@ def _flat_outputs(tensor_list, code):
     key = (t0.dtype, t0.device, shapes, _layout_settings())
     fo = _FLAT_OUTPUTS.get(key)
     if fo is None:
-        if len(_FLAT_OUTPUTS) >= 16:
-            _FLAT_OUTPUTS.pop(next(iter(_FLAT_OUTPUTS)))
-        fo = _FLAT_OUTPUTS[key] = _FlatOutputs(shapes, [t.numel() for t in tensor_list], code, t0.dtype, t0.device)
-        fo.cp = _lib.i64_array(fo.numels)
-        fo.code = code
-        fo.last = (None, None)  # (pointer list, its ptr_array) of the previous call
+        fo = _cache_put(_FLAT_OUTPUTS, key,
+                        _FlatOutputs(shapes, [t.numel() for t in tensor_list], code, t0.dtype, t0.device))
     return fo
 
 
+def _take_outputs(tensor_list, code):
+    """(output set object of this list, (void** of its data pointers, keep-alive), flat buffer, views):
+    what every flat entry that reads the list through Python starts from."""
+    fo = _flat_outputs(tensor_list, code)
+    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
+    return (fo, pp) + fo.take()
+
+
+def _flat_issue(fo, pp, n, flat, device, scale):
+    """The flat call itself: tips_fused_allreduce_flat of the n tensors at void** pp into `flat`, a
+    buffer of output set `fo`, on `device`'s current stream; with scale = (prescale, postscale)
+    tips_fused_allreduce_flat_scaled, the factors inside each bucket's sums."""
+    if scale is not None:
+        _lib.call("tips_fused_allreduce_flat_scaled", pp, fo.cp[0], n, fo.code, flat.data_ptr(), float(scale[0]),
+                  float(scale[1]), fo.cur_stream(device).cuda_stream)
+    else:
+        _lib.call("tips_fused_allreduce_flat", pp, fo.cp[0], n, fo.code, flat.data_ptr(),
+                  fo.cur_stream(device).cuda_stream)
+
+
 def _flat_run(fo, tensor_list, ptrs, scale=None):
-    """tips_fused_allreduce_flat of `tensor_list` (whose data pointers are `ptrs`) into an output set
-    of `fo` (with scale = (prescale, postscale): tips_fused_allreduce_flat_scaled); returns the outputs."""
+    """The flat call (_flat_issue: plain, or scaled by scale = (prescale, postscale)) of `tensor_list`,
+    whose data pointers are `ptrs`, into an output set of `fo`; returns the outputs."""
     last = fo.last  # (one read: another thread may replace it)
     if ptrs == last[0]:
         pp = last[1]
@@ -458,19 +499,8 @@ def _flat_run(fo, tensor_list, ptrs, scale=None):
         pp = _lib.ptr_array(ptrs)
         fo.last = (ptrs, pp)
     flat, views = fo.take()
-    t0 = tensor_list[0]
-    if scale is not None:
-        _lib.call("tips_fused_allreduce_flat_scaled", pp[0], fo.cp[0], len(ptrs), fo.code, flat.data_ptr(),
-                  float(scale[0]), float(scale[1]), _torch_mod().cuda.current_stream(t0.device).cuda_stream)
-        return views
-    _lib.call("tips_fused_allreduce_flat", pp[0], fo.cp[0], len(ptrs), fo.code, flat.data_ptr(),
-              _torch_mod().cuda.current_stream(t0.device).cuda_stream)
+    _flat_issue(fo, pp[0], len(ptrs), flat, tensor_list[0].device, scale)
     return views
-
-
-def _torch_mod():
-    import torch
-    return torch
 
 
 # c10::ScalarType -> tips dtype code (Float, Double, Int, Long, Half, BFloat16)
@@ -478,17 +508,10 @@ _ST_CODES = {6: _lib.FLOAT32, 7: _lib.FLOAT64, 3: _lib.INT32, 4: _lib.INT64, 5: 
 _LIST_BUFS = threading.local()  # .d: n -> (pointer array, count array, their addresses), per thread:
                                 # the library call releases the GIL while it reads them
 _FAST_FLAT = {}   # (scalar type, device, n, shape hash, layout settings) -> (_FlatOutputs, count bytes)
-_CUR_STREAM = None
 
 
-def _dev_list_flat(tensor_list, scale=None):
-    """fused_allreduce_flat of a list of dense, contiguous device tensors of one dtype on one
-    device, with the per-tensor host work in C++ (_fast.dev_list: data pointers, counts, a hash of
-    the shapes): the outputs, or None when the list is not such a list (the caller's general path
-    then inspects it tensor by tensor). A training loop hands over fresh gradient tensors every
-    step; this costs tens of nanoseconds per tensor where reading them through Python cost ~0.2 us."""
-    global _CUR_STREAM
-    n = len(tensor_list)
+def _list_scratch(n):
+    """This thread's (pointer array, count array, their addresses) for _fast.dev_list of n tensors."""
     mine = getattr(_LIST_BUFS, "d", None)
     if mine is None:
         mine = _LIST_BUFS.d = {}
@@ -496,70 +519,59 @@ def _dev_list_flat(tensor_list, scale=None):
     if bufs is None:
         import ctypes
         pa, na = (ctypes.c_void_p * n)(), (ctypes.c_int64 * n)()
-        if len(mine) >= 16:
-            mine.pop(next(iter(mine)))
-        bufs = mine[n] = (pa, na, ctypes.addressof(pa), ctypes.addressof(na))
+        bufs = _cache_put(mine, n, (pa, na, ctypes.addressof(pa), ctypes.addressof(na)))
+    return bufs
+
+
+def _fast_list(tensor_list, want=None):
+    """(the _FlatOutputs of the list, the scratch holding its data pointers and counts) of a list of
+    dense, contiguous device tensors of one dtype (of dtype code `want`, when given) on one device,
+    with the per-tensor host work in C++ (_fast.dev_list: data pointers, counts, a hash of the
+    shapes); None when the list is not such a list. A training loop hands over fresh gradient tensors
+    every step; this costs tens of nanoseconds per tensor where reading them through Python cost
+    ~0.2 us."""
+    n = len(tensor_list)
+    try:
+        bufs = _LIST_BUFS.d[n]  # (_list_scratch's entry, read without the call on the per-step path)
+    except (AttributeError, KeyError):
+        bufs = _list_scratch(n)
     r = _fast.dev_list(tensor_list, bufs[2], bufs[3], 1, n)
-    if r is None or r[0] not in _ST_CODES:
+    if r is None:
+        return None
+    code = _ST_CODES.get(r[0])
+    if code is None or (want is not None and code != want):
         return None
     import ctypes
     key = (r[0], r[1], n, r[2], _layout_settings())
     hit = _FAST_FLAT.get(key)
     counts = ctypes.string_at(bufs[3], 8 * n)
     if hit is None or hit[1] != counts:
-        fo = _flat_outputs(tensor_list, _ST_CODES[r[0]])
-        if len(_FAST_FLAT) >= 16:
-            _FAST_FLAT.pop(next(iter(_FAST_FLAT)))
-        _FAST_FLAT[key] = hit = (fo, counts)
-    fo = hit[0]
+        hit = _cache_put(_FAST_FLAT, key, (_flat_outputs(tensor_list, code), counts))
+    return hit[0], bufs
+
+
+def _dev_list_flat(tensor_list, scale=None):
+    """fused_allreduce_flat of a list _fast_list takes: the outputs, or None when the list is not
+    such a list (the caller's general path then inspects it tensor by tensor)."""
+    hit = _fast_list(tensor_list)
+    if hit is None:
+        return None
+    fo, bufs = hit
     flat, views = fo.take()
-    if _CUR_STREAM is None:
-        import torch
-        _CUR_STREAM = torch.cuda.current_stream
-    if scale is not None:  # (prescale, postscale): the factors inside each bucket's sums
-        _lib.call("tips_fused_allreduce_flat_scaled", bufs[0], fo.cp[0], n, fo.code, flat.data_ptr(), float(scale[0]),
-                  float(scale[1]), _CUR_STREAM(tensor_list[0].device).cuda_stream)
-        return views
-    _lib.call("tips_fused_allreduce_flat", bufs[0], fo.cp[0], n, fo.code, flat.data_ptr(),
-              _CUR_STREAM(tensor_list[0].device).cuda_stream)
+    _flat_issue(fo, bufs[0], len(tensor_list), flat, tensor_list[0].device, scale)
     return views
 
 
 def _dev_list_cast(tensor_list, wire=_lib.FLOAT16, scale=None):
-    """fused_allreduce_cast of a list of dense, contiguous float32 device tensors on one device,
-    with the per-tensor host work in C++ as _dev_list_flat's (Compression.fp16's fast path in
+    """fused_allreduce_cast of a float32 list _fast_list takes (Compression.fp16's fast path in
     allreduce_grads); the float32 outputs, or None when the list is not such a list."""
-    global _CUR_STREAM
-    n = len(tensor_list)
-    mine = getattr(_LIST_BUFS, "d", None)
-    if mine is None:
-        mine = _LIST_BUFS.d = {}
-    bufs = mine.get(n)
-    if bufs is None:
-        import ctypes
-        pa, na = (ctypes.c_void_p * n)(), (ctypes.c_int64 * n)()
-        if len(mine) >= 16:
-            mine.pop(next(iter(mine)))
-        bufs = mine[n] = (pa, na, ctypes.addressof(pa), ctypes.addressof(na))
-    r = _fast.dev_list(tensor_list, bufs[2], bufs[3], 1, n)
-    if r is None or _ST_CODES.get(r[0]) != _lib.FLOAT32:
+    hit = _fast_list(tensor_list, _lib.FLOAT32)
+    if hit is None:
         return None
-    import ctypes
-    key = (r[0], r[1], n, r[2], _layout_settings())
-    hit = _FAST_FLAT.get(key)
-    counts = ctypes.string_at(bufs[3], 8 * n)
-    if hit is None or hit[1] != counts:
-        fo = _flat_outputs(tensor_list, _lib.FLOAT32)
-        if len(_FAST_FLAT) >= 16:
-            _FAST_FLAT.pop(next(iter(_FAST_FLAT)))
-        _FAST_FLAT[key] = hit = (fo, counts)
-    fo = hit[0]
+    fo, bufs = hit
     flat, views = fo.take()
-    if _CUR_STREAM is None:
-        import torch
-        _CUR_STREAM = torch.cuda.current_stream
-    _lib.call("tips_fused_allreduce_cast", bufs[0], _out_ptrs(fo, flat), fo.cp[0], n, _lib.FLOAT32, wire,
-              _CUR_STREAM(tensor_list[0].device).cuda_stream)
+    _lib.call("tips_fused_allreduce_cast", bufs[0], _out_ptrs(fo, flat), fo.cp[0], len(tensor_list), _lib.FLOAT32, wire,
+              fo.cur_stream(tensor_list[0].device).cuda_stream)
     if scale is not None:  # unfused: one tips_scale of the float32 output buffer
         scale_(flat, float(scale[0]) * float(scale[1]))
     return views
@@ -574,10 +586,9 @@ def _out_ptrs(fo, flat):
     if hit is None:
         import ctypes
         import numpy as np
-        arr = np.asarray(fo.offs, dtype=np.uint64) * np.uint64(fo.es) + np.uint64(base)
-        if len(cache) >= 2 * _FlatOutputs.MAX_SETS:
-            cache.pop(next(iter(cache)))
-        hit = cache[base] = (arr, ctypes.cast(arr.ctypes.data, ctypes.POINTER(ctypes.c_void_p)))
+        arr = np.asarray(fo.offs, dtype=np.uint64) + np.uint64(base)
+        hit = _cache_put(cache, base, (arr, ctypes.cast(arr.ctypes.data, ctypes.POINTER(ctypes.c_void_p))),
+                         2 * fo.MAX_SETS)
     return hit[1]
 
 
@@ -623,17 +634,15 @@ def fused_adasum_flat(tensor_list):
         check_adasum_tensor(t, "fused_adasum_flat")
     basics.init()
     code = _check_fusable(tensor_list, "fused_adasum_flat")
-    fo = _flat_outputs(tensor_list, code)
-    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
-    flat, views = fo.take()
+    fo, pp, flat, views = _take_outputs(tensor_list, code)
     _lib.call("tips_fused_allreduce_adasum_flat", pp[0], fo.cp[0], len(tensor_list), code, flat.data_ptr(),
-              _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+              fo.cur_stream(tensor_list[0].device).cuda_stream)
     return views
 
 
 def is_mxfp8_tensor(t):
     """A tensor the MXFP8 collectives take: a dense float32 device tensor."""
-    return tensors.is_torch(t) and t.is_cuda and not t.is_sparse and t.dtype == _torch_mod().float32
+    return tensors.is_torch(t) and t.is_cuda and not t.is_sparse and t.dtype == _torch().float32
 
 
 def _check_mxfp8_list(tensor_list, what):
@@ -665,7 +674,7 @@ def mxfp8_quantize(tensor_list, wire=None):
     """The MXFP8 wire buffer (a uint8 device tensor) of a list of float32 device tensors
     (tips_mxfp8_quantize): one e4m3fn byte per flat element, one power-of-two scale byte per block of
     32; every byte of the buffer is written. `wire`: a 16-B aligned uint8 tensor to fill."""
-    import torch
+    torch = _torch()
     _check_mxfp8_list(tensor_list, "mxfp8_quantize")
     counts = [t.numel() for t in tensor_list]
     elems, _ = mxfp8_flat_elems(counts)
@@ -726,11 +735,9 @@ def fused_allreduce_mxfp8(tensor_list, factor=1.0):
         return []
     _check_mxfp8_list(tensor_list, "fused_allreduce_mxfp8")
     basics.init()
-    fo = _flat_outputs(tensor_list, _lib.FLOAT32)
-    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
-    flat, views = fo.take()
+    fo, pp, flat, views = _take_outputs(tensor_list, _lib.FLOAT32)
     _lib.call("tips_fused_allreduce_mxfp8_flat", pp[0], fo.cp[0], len(tensor_list), flat.data_ptr(), float(factor),
-              _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+              fo.cur_stream(tensor_list[0].device).cuda_stream)
     return views
 
 
@@ -751,7 +758,7 @@ def mxfp8_quantize_ef(tensor_list, residual, wire=None):
     residual = c - dequantise(c) is left for the next step, +0 over a poisoned block. `residual`: a
     float32 device tensor of round_up(E, 256) elements at the flat layout's positions, 16-B aligned,
     zeros before the first step; updated in place."""
-    import torch
+    torch = _torch()
     _check_mxfp8_list(tensor_list, "mxfp8_quantize_ef")
     _check_mxfp8_state(residual, "residual")
     counts = [t.numel() for t in tensor_list]
@@ -807,11 +814,9 @@ def fused_allreduce_mxfp8_ef(tensor_list, state, factor=1.0):
     _check_mxfp8_list(tensor_list, "fused_allreduce_mxfp8_ef")
     _check_mxfp8_state(state, "state")
     basics.init()
-    fo = _flat_outputs(tensor_list, _lib.FLOAT32)
-    pp = _lib.ptr_array([t.data_ptr() for t in tensor_list])
-    flat, views = fo.take()
+    fo, pp, flat, views = _take_outputs(tensor_list, _lib.FLOAT32)
     _lib.call("tips_fused_allreduce_mxfp8_ef_flat", pp[0], fo.cp[0], len(tensor_list), flat.data_ptr(), float(factor),
-              state.data_ptr(), state.numel() * 4, _torch_mod().cuda.current_stream(tensor_list[0].device).cuda_stream)
+              state.data_ptr(), state.numel() * 4, fo.cur_stream(tensor_list[0].device).cuda_stream)
     return views
 
 
@@ -842,27 +847,21 @@ def fused_allreduce_host(tensor_list, out_list=None):
     return outs
 
 
-class _HostFlatOutputs(object):
+class _HostFlatOutputs(_OutputSets):
     """Output sets of fused_allreduce_host_flat for one host list signature (numpy, or CPU torch):
     one flat host buffer laid out as tips_fused_layout, page-locked once (tips_host_register) so
     the device writes the sums straight into it, and one view of it per tensor. A set is handed out
     again once every output of it has been released (as _FlatOutputs: no reference to a view, no
     other array or tensor on its memory)."""
 
-    MAX_SETS = 4
-
     def __init__(self, shapes, numels, code, dtype, is_torch):
-        import ctypes
-        cp, _keep = _lib.i64_array(numels)
-        offs = (ctypes.c_int64 * len(numels))()
-        self.total = max(256, _lib.check("tips_fused_layout", _lib.lib().tips_fused_layout(cp, len(numels), code, offs)))
-        self.cp = _lib.i64_array(numels)
-        self.code, self.numels, self.shapes, self.dtype, self.is_torch = code, numels, shapes, dtype, is_torch
+        _OutputSets.__init__(self, numels, code)
+        self.total = max(256, self.total)
+        self.shapes, self.dtype, self.is_torch = shapes, dtype, is_torch
         self.es = _itemsize(dtype, is_torch)
-        self.offs = [int(o) for o in offs]
-        self.sets = []
-        self.last = (None, None)  # (pointer list, its ptr_array) of the previous call
-        self.lock = threading.Lock()
+
+    def _released(self, s):
+        return self._refs(s) == s[2]
 
     def _refs(self, s):
         """(references to the flat buffer, most references to one view) of set s. Measured the same
@@ -871,41 +870,33 @@ class _HostFlatOutputs(object):
         made from one (numpy collapses every view's .base to the owner; torch counts storage users)."""
         import sys
         if self.is_torch:
-            import torch
-            n = torch._C._storage_Use_Count(s[0].untyped_storage()._cdata)
+            n = _torch()._C._storage_Use_Count(s[0].untyped_storage()._cdata)
         else:
             n = sys.getrefcount(s[0])
         return n, max(map(sys.getrefcount, s[1]), default=0)
 
-    def take(self):
-        """(flat buffer, a new list of its views): made before the library call releases the GIL,
-        as _FlatOutputs.take, under the object's lock."""
-        with self.lock:
-            for s in self.sets:
-                if self._refs(s) == s[2]:
-                    return s[0], list(s[1])
-            import numpy as np
-            mem = np.empty(self.total, dtype=np.uint8)
-            if self.is_torch:
-                import torch
-                flat = torch.from_numpy(mem)  # (the storage keeps `mem` alive: see _register_until_freed)
-                views = [flat[o:o + n * self.es].view(self.dtype).view(shp)
-                         for o, n, shp in zip(self.offs, self.numels, self.shapes)]
-            else:
-                flat = mem
-                views = [flat[o:o + n * self.es].view(self.dtype).reshape(shp)
-                         for o, n, shp in zip(self.offs, self.numels, self.shapes)]
-            if len(self.sets) < self.MAX_SETS:
-                # a kept set is page-locked while its memory lives (the device's D2H lands in it
-                # directly); one past MAX_SETS is not (it is freed with its last output)
-                _register_until_freed(mem, self.total)
-                del mem
-                st = [flat, views, None]
-                del flat, views  # (the baseline counts the set's own references only)
-                st[2] = self._refs(st)
-                self.sets.append(st)
-                return st[0], list(st[1])
+    def _new_set(self, keep):
+        import numpy as np
+        mem = np.empty(self.total, dtype=np.uint8)
+        if self.is_torch:
+            flat = _torch().from_numpy(mem)  # (the storage keeps `mem` alive: see _register_until_freed)
+            views = [flat[o:o + n * self.es].view(self.dtype).view(shp)
+                     for o, n, shp in zip(self.offs, self.numels, self.shapes)]
+        else:
+            flat = mem
+            views = [flat[o:o + n * self.es].view(self.dtype).reshape(shp)
+                     for o, n, shp in zip(self.offs, self.numels, self.shapes)]
+        if not keep:
             return flat, views
+        # a kept set is page-locked while its memory lives (the device's D2H lands in it
+        # directly); one past MAX_SETS is not (it is freed with its last output)
+        _register_until_freed(mem, self.total)
+        del mem
+        st = [flat, views, None]
+        del flat, views  # (the baseline counts the set's own references only)
+        st[2] = self._refs(st)
+        self.sets.append(st)
+        return st[0], list(st[1])
 
 
 def _register_until_freed(mem, nbytes):
@@ -930,8 +921,7 @@ def _unregister(ptr):
 
 def _itemsize(dtype, is_torch):
     if is_torch:
-        import torch
-        return torch.empty((), dtype=dtype).element_size()
+        return _torch().empty((), dtype=dtype).element_size()
     import numpy as np
     return np.dtype(dtype).itemsize
 
@@ -967,10 +957,8 @@ def _host_flat_outputs(srcs):
     key = (str(srcs[0].dtype), is_torch, shapes, _layout_settings())
     fo = _HOST_FLAT.get(key)
     if fo is None:
-        if len(_HOST_FLAT) >= 16:
-            _HOST_FLAT.pop(next(iter(_HOST_FLAT)))
-        fo = _HOST_FLAT[key] = _HostFlatOutputs(shapes, [tensors.numel(s) for s in srcs],
-                                                tensors.dtype_code(srcs[0]), srcs[0].dtype, is_torch)
+        fo = _cache_put(_HOST_FLAT, key, _HostFlatOutputs(shapes, [tensors.numel(s) for s in srcs],
+                                                     tensors.dtype_code(srcs[0]), srcs[0].dtype, is_torch))
     return fo
 
 
@@ -1015,17 +1003,13 @@ class FusedList(object):
         self._arrays = None
         self._cp = _lib.i64_array(self._counts)
         self._count_bytes = self._cp[1].tobytes()  # (little-endian int64, as _fast.dev_list writes them)
-        self._tls = threading.local()  # per-thread scratch: the library call releases the GIL
 
     def allreduce_(self, tensor_list):
         if not tensor_list:
             return tensor_list
         import ctypes
         n = len(tensor_list)
-        sc = getattr(self._tls, "sc", None)
-        if sc is None or len(sc[0]) != n:
-            pa, na = (ctypes.c_void_p * n)(), (ctypes.c_int64 * n)()
-            sc = self._tls.sc = (pa, na, ctypes.addressof(pa), ctypes.addressof(na))
+        sc = _list_scratch(n)  # (this thread's: another thread's call can run before the compare below)
         # pointers, counts and dtype read in C++ (_fast.dev_list); the Python checks below only when
         # the list is not one dtype of dense contiguous device tensors, or its pointers changed
         r = _fast.dev_list(tensor_list, sc[2], sc[3], 1, n)
@@ -1170,13 +1154,13 @@ def allgather_async(tensor, name):
     torch_src = tensors.is_torch(src)
     req_stream = None
     if torch_src and src.is_cuda:
-        import torch
+        torch = _torch()
         req_stream = torch.cuda.current_stream(src.device)  # the stream the request runs on
 
     def alloc(_ctx, nbytes):
         if torch_src:
             import contextlib
-            import torch
+            torch = _torch()
             # allocated on the negotiation thread, but the transfer writes it on the request's
             # stream: allocate under that stream, so the caching allocator ties the block to it
             with torch.cuda.stream(req_stream) if req_stream is not None else contextlib.nullcontext():
@@ -1193,7 +1177,7 @@ def allgather_async(tensor, name):
         if "buf" in box:
             return box.pop("buf").view(src.dtype).reshape(out_shape)
         if torch_src:
-            import torch
+            torch = _torch()
             return torch.empty(out_shape, dtype=src.dtype, device=src.device)
         return np.empty(out_shape, dtype=src.dtype)
 
@@ -1366,7 +1350,7 @@ def grouped_reducescatter_op(tensor_list, op="Average", prescale_factor=1.0, pos
     if mxfp8 and op not in ("Average", "Sum"):
         raise ValueError("op=%s does not combine with the MXFP8 wire: it carries SUM (and Average) only" % op)
     basics.init()
-    torch = tensors._torch()
+    torch = _torch()
     p, r = basics.size(), basics.rank()
     if op == "Average":
         post = post / p
